@@ -20,6 +20,12 @@ region; random-init weights of the exact Llama-3-70B architecture in bf16.
 Scaling is WEAK: --batch-per-gpu sequences per GPU (global batch = batch_per_gpu x N).
 value = generated tokens across the node / wall time of the K timed steps (max over ranks).
 
+A plain run does only what that figure needs: set-up (engine, graph capture, prefill), --warmup
+steps, the --steps timed steps, one JSON line. --dump-outputs DIR also writes the last timed
+step's results (sequence ids, their new tokens, the decode logits) as DIR/<name>.npy, so that
+two builds can be compared output for output: the same arguments give the same prompts and
+weights. --full is where anything measured beyond the headline belongs (nothing today).
+
 BASELINE.json configs are one flag each (--baseline-config):
   1 GPT-2 small, 2-stage layer split, CPU/gloo, 2 ranks      3 Llama-3-70B PP=8
   2 Llama-3-8B on one GPU                                     4 Llama-3-70B TP=2 x PP=4
@@ -92,7 +98,52 @@ def build_parser() -> argparse.ArgumentParser:
                     help="single-stage layouts: host waits for each step's tokens before scheduling the "
                          "next (default: EngineConfig.async_decode, the next step overlaps the host work)")
     ap.add_argument("--out", default=None, help="also write the JSON line here")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                         "(float32; see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run whatever the benchmark measures beyond its headline figure; a plain run "
+                         "sets up, warms up, times the steps and prints the result line (today the benchmark "
+                         "measures nothing beyond that, so the runs are the same)")
     return ap
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, eng, out, vocab: int) -> dict:
+    """Write what the last timed step gave its caller as <path>/<name>.npy (float32):
+      seq_ids     [B]        request ids of the step's rows (StepOutput.rids)
+      new_tokens  [B]        the token each of them received (StepOutput.new_tokens)
+      logits      [B, vocab] the decode logits of the forward that step launched, read from the decode
+                             graph's static output (single-stage hipGraph runs only: other paths do
+                             not keep their logits)
+      next_tokens [B]        the ids the graph's sampler drew from those logits. With asynchronous
+                             decode a step hands out the tokens of the forward launched one step
+                             earlier, so these are what one more step would return
+    Prompts and weights are seeded, so the same arguments give the same inputs in every run.
+    An array over the size budget is cut to a seeded sample of its rows."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    arrays = {"seq_ids": np.asarray(out.rids, dtype=np.float32),
+              "new_tokens": np.asarray(out.new_tokens, dtype=np.float32)}
+    g = eng.runner.graphs.get(eng.runner.bucket_of(len(out.rids))) if eng.runner.use_graphs else None
+    if g is not None and not isinstance(g, list) and g.graph is not None and eng.model.last:
+        logits = g.output[:len(out.rids), :vocab]
+        if g.ids is not None:
+            arrays["next_tokens"] = g.ids[:len(out.rids)].cpu().numpy().astype(np.float32)
+        rows = max(1, min(logits.shape[0], (DUMP_LIMIT_BYTES - (1 << 20)) // (4 * logits.shape[1])))
+        if rows < logits.shape[0]:
+            keep = torch.randperm(logits.shape[0], generator=torch.Generator().manual_seed(0))[:rows].sort().values
+            arrays["logits_rows"] = keep.numpy().astype(np.float32)
+            logits = logits[keep.to(logits.device)]
+        arrays["logits"] = logits.float().cpu().numpy()
+    assert sum(v.nbytes for v in arrays.values()) <= DUMP_LIMIT_BYTES
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), v)
+    return {k: list(v.shape) for k, v in arrays.items()}
 
 
 def resolve(a) -> None:
@@ -343,6 +394,8 @@ def run(a) -> int:
                                                          for t in eng.model.packed.values()) / 1e9, 1)},
     }
     if rank == 0:
+        if a.dump_outputs:
+            res["dumped_outputs"] = dump_outputs(a.dump_outputs, eng, out, cfg.vocab_size)
         line = json.dumps(res)
         print(line, flush=True)
         if a.out:
