@@ -72,7 +72,8 @@ def cmd_generate(a) -> int:
     snap_every = a.snapshot_every if a.snapshot_dir else 0
     llm = LLM(a.model, plan=_strategy(a.plan),
               engine_config=EngineConfig(max_batch=8, max_seq_len=a.max_seq_len, use_graphs=not a.no_graphs,
-                                         snapshot_dir=a.snapshot_dir, snapshot_every=snap_every),
+                                         snapshot_dir=a.snapshot_dir, snapshot_every=snap_every,
+                                         weight_dtype=a.weight_dtype),
               tokenizer=a.tokenizer)
     prompts = a.prompt or ["Hello"]
     params = SamplingParams(max_tokens=a.max_tokens, temperature=a.temperature, seed=a.seed, ignore_eos=True)
@@ -110,7 +111,8 @@ def cmd_serve(a) -> int:
     from .server import serve
 
     llm = LLM(a.model, plan=_strategy(a.plan), tokenizer=a.tokenizer,
-              engine_config=EngineConfig(max_batch=a.max_batch, max_seq_len=a.max_seq_len))
+              engine_config=EngineConfig(max_batch=a.max_batch, max_seq_len=a.max_seq_len,
+                                         weight_dtype=a.weight_dtype))
     serve(llm, a.host, a.port)
     return 0
 
@@ -198,6 +200,8 @@ def main(argv=None) -> int:
     g.add_argument("--plan", default="auto")
     g.add_argument("--tokenizer", default=None)
     g.add_argument("--no-graphs", action="store_true")
+    g.add_argument("--weight-dtype", default="auto", choices=["auto", "bf16", "fp8"],
+                   help="dense projection weights: bf16, or fp8 (weight-only e4m3); auto = BFLY_WEIGHT_DTYPE")
     g.add_argument("--snapshot-dir", default=None,
                    help="write request-state snapshots here; a restarted job (launch --max-restarts) resumes from them")
     g.add_argument("--snapshot-every", type=int, default=4, help="engine steps between snapshots")
@@ -210,6 +214,8 @@ def main(argv=None) -> int:
     s.add_argument("--port", type=int, default=8000)
     s.add_argument("--max-batch", type=int, default=64)
     s.add_argument("--max-seq-len", type=int, default=4096)
+    s.add_argument("--weight-dtype", default="auto", choices=["auto", "bf16", "fp8"],
+                   help="dense projection weights: bf16, or fp8 (weight-only e4m3); auto = BFLY_WEIGHT_DTYPE")
     s.set_defaults(fn=cmd_serve)
     b = sub.add_parser("bench", add_help=False)
     b.add_argument("rest", nargs=argparse.REMAINDER)

@@ -217,6 +217,11 @@ class EngineConfig:
     # |x| <= 448): half the KV bytes per token, so twice the cached tokens and half the KV
     # traffic of a decode step; attention math stays bf16 (csrc/include/bfly_kv.h)
     kv_cache_dtype: str = "auto"
+    # element type of the dense projection weights (QKV, O, gate/up, down): "bf16", or "fp8"
+    # (weight-only e4m3 codes with one f32 scale per output row, quantised by the engine once the
+    # weights are final: half the weight bytes streamed per decode step, the freed HBM goes to
+    # KV pages; activations and accumulation stay as they are). "auto": the BFLY_WEIGHT_DTYPE flag.
+    weight_dtype: str = "auto"
     # context-parallel prefill across data-parallel replicas (pp == 1, no EP): a prompt of at
     # least this many tokens is prefilled by ALL dp replicas together (ring or Ulysses
     # attention, parallel/context_parallel.py), its K/V collected in the cache of the replica

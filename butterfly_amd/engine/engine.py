@@ -124,6 +124,17 @@ class LLMEngine:
         if model is None:
             self.model.init_random(engine_cfg.seed)
         self.eos = eos_token_id
+        # ---- weight-only quantisation (before the KV cache is sized: the HBM it frees goes to
+        # KV pages; the FP8 GEMM's scratch is taken first so that the budget below sees it)
+        self.weight_dtype = weight_dtype(engine_cfg.weight_dtype)
+        if self.weight_dtype != "bf16":
+            self.model.quantize_weights(self.weight_dtype)
+            if self.device.type == "cuda":
+                ops.reserve_w8_workspace(self.device, max(engine_cfg.max_prefill_tokens, engine_cfg.max_batch),
+                                         self.model.w8_shapes())
+                torch.cuda.empty_cache()
+        elif getattr(self.model, "weight_dtype", "bf16") != "bf16":
+            self.weight_dtype = self.model.weight_dtype      # handed an already quantised model
         # ---- KV cache sizing ------------------------------------------------------------
         bs = engine_cfg.block_size
         self.kv_dtype = kv_cache_dtype(engine_cfg.kv_cache_dtype, self.model.dtype)
@@ -201,7 +212,7 @@ class LLMEngine:
                                   max_n=self._max_gemm_n(), max_k=self._max_gemm_k(),
                                   max_batch=max(engine_cfg.graph_batch_sizes + [engine_cfg.max_batch]),
                                   max_ctx=engine_cfg.max_seq_len, num_kv_heads=d.hkv, head_dim=cfg.head_dim,
-                                  shapes=self.model.gemm_shapes())
+                                  shapes=self.model.gemm_shapes(), w8_shapes=self.model.w8_shapes())
         buckets = [b for b in engine_cfg.graph_batch_sizes if b <= engine_cfg.max_batch] or [engine_cfg.max_batch]
         if self.async_pp and self.scheduler.group_batch not in buckets:
             buckets.append(self.scheduler.group_batch)    # a full group replays one graph
@@ -995,6 +1006,18 @@ class LLMEngine:
         while self.has_unfinished_global():
             self.step()
         return [self.requests[r].output for r in rids]
+
+
+def weight_dtype(name: str) -> str:
+    """EngineConfig.weight_dtype -> "bf16" | "fp8" ("auto": the BFLY_WEIGHT_DTYPE flag)."""
+    if name in (None, "auto"):
+        name = flags.get("BFLY_WEIGHT_DTYPE")
+    name = str(name).strip().lower()
+    if name in ("bf16", "bfloat16"):
+        return "bf16"
+    if name in ("fp8", "fp8_e4m3", "e4m3"):
+        return "fp8"
+    raise ValueError(f"unknown weight_dtype {name!r} (auto | bf16 | fp8)")
 
 
 def kv_cache_dtype(name: str, model_dtype: torch.dtype) -> torch.dtype:

@@ -98,6 +98,10 @@ class TransformerLM:
         self.p: dict[str, torch.Tensor] = {}
         # K-tile-blocked copies of the gate/up weights for the decode GEMMs (pack_decode_weights)
         self.packed: dict[str, torch.Tensor] = {}
+        # f32 row scales of the FP8-quantised projections (quantize_weights); self.p[name] then
+        # holds the e4m3 codes
+        self.wscale: dict[str, torch.Tensor] = {}
+        self.weight_dtype = "bf16"
         self._alloc()
         self.cos = self.sin = None
         if cfg.pos_emb == "rope":
@@ -170,7 +174,7 @@ class TransformerLM:
             for i in self.layer_ids:
                 k = f"l{i}.{kind}"
                 w = self.p.get(k)
-                if (w is not None and w.shape[0] % 256 == 0 and w.shape[1] % 64 == 0
+                if (w is not None and k not in self.wscale and w.shape[0] % 256 == 0 and w.shape[1] % 64 == 0
                         and any(torch.ops.bfly.gemm_packed_check(m, w.shape[0], w.shape[1], self._PACK_EPI.get(kind, 0)) == 0
                                 for m in (1, 16, 64, 128, 256, 512))):
                     names.append(k)
@@ -209,10 +213,55 @@ class TransformerLM:
         return self.p["head"] if "head" in self.p else self.p["embed"]
 
     def local_bytes(self) -> int:
-        return sum(t.numel() * t.element_size() for t in self.p.values())
+        return sum(t.numel() * t.element_size() for t in list(self.p.values()) + list(self.wscale.values()))
+
+    _W8_KINDS = ("qkv_w", "o_w", "gu_w", "down_w")
+
+    def quantize_weights(self, weight_dtype: str = "fp8") -> int:
+        """Replace the four dense projections of every local layer by FP8 e4m3 codes with one
+        f32 scale per (local shard) output row (ops.quantize_fp8), one tensor at a time so the
+        peak stays at the bf16 model's. Embedding, LM head and norms keep the model dtype. The
+        scales are per local row: a row-parallel shard (O, down) scales its own partial sum
+        before the all-reduce, so the quantised values depend on the TP split. Quantised
+        projections return plain tensors: the split-K / row-scale consumer fusions of the bf16
+        plans and the packed decode copies are off. Call after the weights are final (random
+        init or checkpoint load). Returns the bytes freed."""
+        if weight_dtype in ("bf16", None):
+            return 0
+        if weight_dtype != "fp8":
+            raise ValueError(f"quantize_weights: unknown weight dtype {weight_dtype!r} (fp8)")
+        c = self.cfg
+        if c.is_moe:
+            raise ValueError("FP8 weights: MoE models are not supported (no FP8 grouped expert GEMM)")
+        if c.bias:
+            raise ValueError("FP8 weights: models with linear biases are not supported (the FP8 GEMM has no bias epilogue)")
+        if c.act != "silu":
+            raise ValueError("FP8 weights: only SwiGLU models are supported (the FP8 GEMM has no GELU FFN path)")
+        if self.wscale:
+            return 0
+        if self.packed:
+            raise ValueError("FP8 weights: quantise before pack_decode_weights")
+        before = self.local_bytes()
+        for i in self.layer_ids:
+            for kind in self._W8_KINDS:
+                name = f"l{i}.{kind}"
+                code, scale = ops.quantize_fp8(self.p[name])
+                self.p[name] = code
+                self.wscale[name] = scale
+        self.weight_dtype = "fp8"
+        self.defer_qkv = self.defer_reduce = False
+        self.rowscale_rows = 0
+        return before - self.local_bytes()
+
+    def w8_shapes(self) -> list:
+        """(N, K) of the FP8-quantised projections (ops.reserve_workspace)."""
+        return sorted({tuple(self.p[k].shape) for k in self.wscale})
 
     def logical_params(self) -> list[LogicalParam]:
         """Every logical (HF-style) parameter slice this rank holds."""
+        if self.wscale:
+            raise RuntimeError("logical_params: the model holds FP8-quantised weights; checkpoints are saved "
+                               "from / loaded into an unquantised model (quantise after loading)")
         c, d, s = self.cfg, self.dims, self.shard
         h, D = c.hidden_size, c.head_dim
         tp0 = s.tp_rank == 0
@@ -416,6 +465,15 @@ class TransformerLM:
             delta, partial = self._ffn(pre, x, fb, route)
         return delta, partial
 
+    def _proj(self, name: str, x, epilogue: str = "none", bias=None, defer: bool = False):
+        """One of the four dense projections (qkv / o / gate-up / down) of a layer: the FP8
+        GEMM on its codes and row scales when the weight is quantised (plain bf16 output, no
+        bias), else ops.linear on the bf16 weight and its packed copy."""
+        if name in self.wscale:
+            return ops.linear_w8(x, self.p[name], self.wscale[name], epilogue=epilogue)
+        return ops.linear(x, self.p[name], bias=bias, epilogue=epilogue, defer=defer,
+                          packed=self.packed.get(name))
+
     def _attention_block(self, li: int, pre: str, x: torch.Tensor, fb: ForwardBatch,
                          kv_caches: Optional[list]):
         """normed x [T, h] -> QKV GEMM -> RoPE + KV append -> attention -> O GEMM (TP-partial)."""
@@ -425,8 +483,7 @@ class TransformerLM:
         slots = fb.slots if kc is not None else None
         # split-K reduces are deferred into the consuming kernel (rope_kv / add+rmsnorm)
         # when no all-reduce sits in between (tp == 1)
-        qkv = ops.linear(x, self.p[pre + "qkv_w"], bias=self.p.get(pre + "qkv_b"), defer=self.defer_qkv,
-                         packed=self.packed.get(pre + "qkv_w"))
+        qkv = self._proj(pre + "qkv_w", x, bias=self.p.get(pre + "qkv_b"), defer=self.defer_qkv)
         if c.pos_emb == "rope":
             qkv = ops.rope_kv(qkv, fb.positions, self.cos, self.sin, d.hq, d.hkv, slots, kc, vc)
         elif kc is not None:
@@ -457,8 +514,7 @@ class TransformerLM:
     def _o_proj(self, pre: str, attn: torch.Tensor, T: int):
         d, D = self.dims, self.cfg.head_dim
         o_b = self.p.get(pre + "o_b") if self.shard.tp_rank == 0 else None
-        return ops.linear(attn.view(T, d.hq * D), self.p[pre + "o_w"], bias=o_b, defer=self.defer_reduce,
-                          packed=self.packed.get(pre + "o_w"))
+        return self._proj(pre + "o_w", attn.view(T, d.hq * D), bias=o_b, defer=self.defer_reduce)
 
     # ------------------------------------------------------------------------------------
     # sequence parallelism (TP prefill)
@@ -613,8 +669,8 @@ class TransformerLM:
                 return self.comm.reduce_scatter(out, "ep")[:T], False
             return out, self.tp > 1
         if c.act == "silu":
-            hmid = ops.linear(x, self.p[pre + "gu_w"], epilogue="silu", packed=self.packed.get(pre + "gu_w"))
-            out = ops.linear(hmid, self.p[pre + "down_w"], defer=self.defer_reduce, packed=self.packed.get(pre + "down_w"))
+            hmid = self._proj(pre + "gu_w", x, epilogue="silu")
+            out = self._proj(pre + "down_w", hmid, defer=self.defer_reduce)
         else:
             hmid = ops.linear(x, self.p[pre + "fc_w"], bias=self.p.get(pre + "fc_b"))
             hmid = ops.gelu(hmid)

@@ -171,14 +171,44 @@ def arena_scope(name) -> None:
     _scope.name = name
 
 
+def reserve_w8_workspace(device, max_tokens: int, w8_shapes) -> None:
+    """The FP8 weight-only GEMM's buffers for quantised projections of shapes `w8_shapes`
+    (N, K) at up to `max_tokens` rows: the native kernel's split-K slabs and, when some row
+    count or shape takes the dequantise route, a bf16 scratch of the largest projection and of
+    the largest unscaled GEMM result (SwiGLU projections)."""
+    if not load_library():
+        return
+    w8 = {(int(n), int(k)) for n, k in w8_shapes}
+    if w8:
+        slab, deq, tmp = 0, 0, 0
+        for m in sorted(set(range(1, 257)) | {max_tokens}):
+            if m > max_tokens:
+                continue
+            for n, k in w8:
+                if any(torch.ops.bfly.gemm_w8_check(m, n, k, e) != 0 for e in (0, 2)):
+                    deq = max(deq, n * k)
+                    tmp = max(tmp, m * n)
+                else:
+                    slab = max(slab, torch.ops.bfly.gemm_w8_workspace_size(m, n, k))
+        if slab:
+            _arena.get(device, "gemm_w8", slab // 4 + 1, torch.float32)
+        if deq:
+            _arena.get(device, "w8_deq", deq, torch.bfloat16)
+            _arena.get(device, "w8_tmp", tmp, torch.bfloat16)
+
+
 def reserve_workspace(device, max_tokens: int, max_n: int, max_k: int, max_batch: int = 0,
-                      max_ctx: int = 0, num_kv_heads: int = 0, head_dim: int = 128, shapes=()) -> None:
+                      max_ctx: int = 0, num_kv_heads: int = 0, head_dim: int = 128, shapes=(),
+                      w8_shapes=()) -> None:
     """Pre-size every workspace for problems up to the given bounds (call before capture).
     `shapes`: the model's GEMM weight shapes (N, K); the split-K slab need is the max over them
     and every token-count bucket of the plan table (a tuned plan may split a small projection
-    more than the largest one is split)."""
+    more than the largest one is split). `w8_shapes`: the (N, K) of FP8-quantised projections:
+    sizes the native FP8 GEMM's split-K slabs and, for token counts (or shapes) that take the
+    dequantise route, the bf16 scratch of the largest of them."""
     if not load_library():
         return
+    reserve_w8_workspace(device, max_tokens, w8_shapes)
     ws = 0
     nk = {(int(max_n), int(max_k))} | {(int(n), int(k)) for n, k in shapes}
     for m in sorted({1, 16, 32, 48, 64, 128, 256, 512, max_tokens}):
@@ -509,6 +539,69 @@ def linear(x, w, bias=None, epilogue: str = "none", out=None, defer: bool = Fals
         torch.ops.bfly.gemm_rs(x, w, out, bias, epi, ws, rn.ssp, rn.eps)
     else:
         torch.ops.bfly.gemm(x, w, out, bias, epi, ws)
+    return out
+
+
+def quantize_fp8(w):
+    """FP8 e4m3 weight-only quantisation of a [N, K] weight (ops.reference.quantize_fp8 has the
+    format): returns (code torch.float8_e4m3fn [N, K], scale f32 [N])."""
+    if not _gpu(w):
+        return ref.quantize_fp8(w)
+    if w.dim() != 2 or w.dtype != torch.bfloat16:
+        raise ValueError("quantize_fp8: a 2-D bf16 weight")
+    if w.stride(1) != 1 or w.stride(0) % 8 != 0 or w.data_ptr() % 16 != 0:
+        w = w.contiguous()
+    code = _empty(w.shape[0], w.shape[1], dtype=torch.float8_e4m3fn, device=w.device)
+    scale = _empty(w.shape[0], dtype=torch.float32, device=w.device)
+    torch.ops.bfly.quant_fp8_rows(w, code, scale)
+    return code, scale
+
+
+def dequantize_fp8(code, scale, dtype=None, out=None):
+    """dtype(float(code) * scale[:, None]) (GPU: bf16, dequant_fp8_kernel)."""
+    if not _gpu(code):
+        y = ref.dequantize_fp8(code, scale, dtype or torch.float32)
+        return y if out is None else out.copy_(y)
+    if dtype not in (None, torch.bfloat16):
+        raise ValueError("dequantize_fp8: the GPU kernel writes bf16")
+    if out is None:
+        out = _empty(code.shape[0], code.shape[1], dtype=torch.bfloat16, device=code.device)
+    torch.ops.bfly.dequant_fp8(code, scale, out)
+    return out
+
+
+def linear_w8(x, code, scale, epilogue: str = "none", out=None):
+    """y = (x @ float(code).T) * scale with optional fused SwiGLU epilogue: the FP8 e4m3
+    weight-only counterpart of `linear` (no bias). Shapes and row counts the native kernel
+    takes (gemm_w8_check) stream the codes once (gemm_w8.hip gemm_w8_kernel); every other one
+    widens the codes into the arena's bf16 scratch, runs `linear` on it and scales the result."""
+    if not _gpu(x):
+        return ref.linear_w8(x, code, scale, epilogue, out)
+    if epilogue not in ("none", "silu"):
+        raise ValueError(f"linear_w8: epilogue {epilogue!r} not supported (no bias)")
+    M, K = x.shape
+    N = code.shape[0]
+    epi = EPILOGUES[epilogue]
+    if torch.ops.bfly.gemm_w8_check(M, N, K, epi) == 0:
+        if out is None:
+            out = _empty(M, N // 2 if epilogue == "silu" else N, dtype=x.dtype, device=x.device)
+        need = torch.ops.bfly.gemm_w8_workspace_size(M, N, K)
+        ws = _arena.get(x.device, "gemm_w8", need // 4 + 1, torch.float32) if need else None
+        torch.ops.bfly.gemm_w8(x, code, scale, out, epi, ws, False)
+        return out
+    # bare codes are exact in bf16: the bf16 GEMM runs on them and the scale multiplies its
+    # result (as the native kernel scales its accumulators), then SwiGLU
+    wd = _arena.get(x.device, "w8_deq", N * K, torch.bfloat16)[:N * K].view(N, K)
+    torch.ops.bfly.dequant_fp8(code, None, wd)
+    if out is None:
+        out = _empty(M, N // 2 if epilogue == "silu" else N, dtype=x.dtype, device=x.device)
+    if epilogue == "silu":
+        y = _arena.get(x.device, "w8_tmp", M * N, torch.bfloat16)[:M * N].view(M, N)
+        linear(x, wd, out=y)
+    else:
+        y = linear(x, wd, out=out)
+    if M:
+        torch.ops.bfly.w8_scale_cols(y, scale, out, epi)
     return out
 
 

@@ -328,6 +328,46 @@ def linear(x, w, bias=None, epilogue="none", out=None):
     return out
 
 
+FP8_MAX = 448.0  # largest finite OCP e4m3fn value
+
+
+def quantize_fp8(w):
+    """FP8 e4m3 weight-only quantisation of a [N, K] weight, one f32 scale per output row:
+    scale[n] = absmax(w[n]) / 448 (1 for an all-zero row), code = RNE_e4m3fn(w / scale).
+    Returns (code torch.float8_e4m3fn [N, K], scale f32 [N])."""
+    wf = w.float()
+    amax = wf.abs().amax(dim=1)
+    scale = torch.where(amax > 0, amax / FP8_MAX, torch.ones_like(amax))
+    t = (wf / scale[:, None]).clamp_(-FP8_MAX, FP8_MAX)
+    return t.to(torch.float8_e4m3fn), scale
+
+
+def dequantize_fp8(code, scale, dtype=torch.float32):
+    """dtype(float(code) * scale[:, None]); `code` float8_e4m3fn or its uint8 view."""
+    if code.dtype == torch.uint8:
+        code = code.view(torch.float8_e4m3fn)
+    return (code.float() * scale.float()[:, None]).to(dtype)
+
+
+def linear_w8(x, code, scale, epilogue="none", out=None):
+    """y[m, n] = scale[n] * sum_k x[m, k] * float(code[n, k]) in f32, then the optional SwiGLU
+    epilogue of `linear` (scales are per physical row of the interleaved weight), then rounding
+    to x.dtype."""
+    if code.dtype == torch.uint8:
+        code = code.view(torch.float8_e4m3fn)
+    y = (x.float() @ code.float().t()) * scale.float()
+    if epilogue == "silu":
+        g, u = split_gate_up(y, SILU_INTERLEAVE)
+        y = F.silu(g) * u
+    elif epilogue != "none":
+        raise ValueError(f"linear_w8: epilogue {epilogue!r} not supported (no bias)")
+    y = y.to(x.dtype)
+    if out is None:
+        return y
+    out.copy_(y)
+    return out
+
+
 def attn_prefill(q, k, v, cu_seqlens, max_seqlen, scale, causal=True, out=None, cu_seqlens_k=None,
                  return_lse=False):
     """q [T, Hq, D], k/v [Tk, Hkv, D]; varlen sequences given by cu_seqlens (int32), keys by

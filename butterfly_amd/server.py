@@ -180,7 +180,8 @@ def create_app(loop: ServingLoop):
 
     @app.get("/v1/models")
     def models():
-        return {"object": "list", "data": [{"id": loop.llm.cfg.name, "object": "model"}]}
+        return {"object": "list", "data": [{"id": loop.llm.cfg.name, "object": "model",
+                                            "weight_dtype": getattr(loop.llm.engine, "weight_dtype", "bf16")}]}
 
     @app.get("/metrics", response_class=PlainTextResponse)
     def metrics():

@@ -104,6 +104,8 @@ define("BFLY_PACKED_KINDS", "gu_w,moe_gu_w,qkv_w,o_w", str, "projection kinds pa
        "priority order: a kind is packed whole or not at all, while the HBM lasts (down_w / moe_down_w also "
        "work: whole-step within noise, profiles/r6_packed/kinds_ab.log; o_w runs its own packed plan where one is "
        "tuned, gemm.hip kPackedTuned)")
+define("BFLY_WEIGHT_DTYPE", "bf16", str, "dense projection weights of engines whose EngineConfig.weight_dtype is "
+       "'auto': bf16, or fp8 (weight-only e4m3 codes with one f32 scale per output row, csrc/kernels/gemm_w8.hip)")
 define("BFLY_MOE_NORM_ROUTE", True, _bool, "MoE layers at tp = 1: the add+RMSNorm over the O projection's split-K "
        "slabs also routes the rows (0: separate moe_route launch)")
 define("BFLY_MOE_GATE_EPILOGUE", True, _bool, "dense MoE decode path: the routing weights applied in the gate/up "

@@ -443,6 +443,92 @@ int64_t gemm_packed(const Tensor& x, const Tensor& wp, Tensor& out, int64_t epil
                                   cur_stream(), any ? &rs : nullptr, false, ws, ws_bytes, defer);
 }
 
+// FP8 e4m3 weight-only linear layers (gemm_w8.hip). Codes are torch.float8_e4m3fn or uint8.
+inline bool is_fp8_code(const Tensor& t) {
+  return t.scalar_type() == at::kFloat8_e4m3fn || t.scalar_type() == at::kByte;
+}
+inline uint8_t* u8(const Tensor& t) { return reinterpret_cast<uint8_t*>(t.data_ptr()); }
+
+void quant_fp8_rows(const Tensor& w, Tensor& code, Tensor& scale) {
+  CHECK_GPU(w); CHECK_BF16(w); CHECK_INNER(w); CHECK_ALIGN16(w);
+  TORCH_CHECK(w.dim() == 2, "quant_fp8_rows: 2-D weight");
+  const int64_t N = w.size(0), K = w.size(1);
+  TORCH_CHECK(K < (1LL << 31) && N < (1LL << 31), "quant_fp8_rows: shape");
+  TORCH_CHECK(code.is_cuda() && is_fp8_code(code) && code.dim() == 2 && code.size(0) == N && code.size(1) == K &&
+                  code.is_contiguous(), "quant_fp8_rows: code [N, K] e4m3 contiguous");
+  CHECK_ALIGN16(code);
+  TORCH_CHECK(scale.is_cuda() && scale.scalar_type() == at::kFloat && scale.numel() == N && scale.is_contiguous(),
+              "quant_fp8_rows: scale [N] f32");
+  c10::DeviceGuard g(w.device());
+  bfly::launch_quant_fp8_rows(bf(w), w.stride(0), N, (int)K, u8(code), scale.data_ptr<float>(), cur_stream());
+}
+
+void dequant_fp8(const Tensor& code, const c10::optional<Tensor>& scale_, Tensor& out) {
+  CHECK_GPU(code); CHECK_BF16(out); CHECK_INNER(out); CHECK_ALIGN16(out); CHECK_ALIGN16(code);
+  TORCH_CHECK(is_fp8_code(code) && code.dim() == 2 && code.is_contiguous(), "dequant_fp8: code [N, K] e4m3 contiguous");
+  const int64_t N = code.size(0), K = code.size(1);
+  TORCH_CHECK(K < (1LL << 31), "dequant_fp8: shape");
+  const float* sp = nullptr;
+  if (scale_.has_value()) {
+    const Tensor& scale = *scale_;
+    TORCH_CHECK(scale.is_cuda() && scale.scalar_type() == at::kFloat && scale.numel() == N && scale.is_contiguous(),
+                "dequant_fp8: scale [N] f32");
+    sp = scale.data_ptr<float>();
+  }
+  TORCH_CHECK(out.is_cuda() && out.dim() == 2 && out.size(0) == N && out.size(1) == K && out.stride(0) % 8 == 0,
+              "dequant_fp8: out [N, K] bf16, row stride % 8");
+  c10::DeviceGuard g(code.device());
+  bfly::launch_dequant_fp8(u8(code), sp, N, (int)K, bf(out), out.stride(0), cur_stream());
+}
+
+void w8_scale_cols(const Tensor& y, const Tensor& scale, Tensor& out, int64_t epilogue) {
+  CHECK_GPU(y); CHECK_BF16(y); CHECK_BF16(out); CHECK_INNER(y); CHECK_INNER(out);
+  CHECK_ALIGN16(y); CHECK_ALIGN16(out); CHECK_ALIGN16(scale);
+  TORCH_CHECK(y.dim() == 2 && out.dim() == 2 && out.is_cuda(), "w8_scale_cols: 2-D operands");
+  const int M = y.size(0), N = y.size(1);
+  TORCH_CHECK(epilogue == bfly::EPI_NONE || epilogue == bfly::EPI_SILU, "w8_scale_cols: epilogue none / silu");
+  TORCH_CHECK(N % 32 == 0 && y.stride(0) % 8 == 0 && out.stride(0) % 8 == 0, "w8_scale_cols: N % 32, row strides % 8");
+  TORCH_CHECK(out.size(0) == M && out.size(1) == (epilogue == bfly::EPI_SILU ? N / 2 : N), "w8_scale_cols: out shape");
+  TORCH_CHECK(scale.is_cuda() && scale.scalar_type() == at::kFloat && scale.numel() == N && scale.is_contiguous(),
+              "w8_scale_cols: scale [N] f32");
+  c10::DeviceGuard g(y.device());
+  bfly::launch_w8_scale_cols(bf(y), y.stride(0), scale.data_ptr<float>(), M, N, (int)epilogue, bf(out), out.stride(0),
+                             cur_stream());
+}
+
+void gemm_w8(const Tensor& x, const Tensor& code, const Tensor& scale, Tensor& out, int64_t epilogue,
+             const c10::optional<Tensor>& workspace, bool any_m, int64_t force_sk) {
+  CHECK_GPU(x); CHECK_BF16(x); CHECK_BF16(out);
+  TORCH_CHECK(x.dim() == 2 && code.dim() == 2 && out.dim() == 2, "gemm_w8: 2-D operands");
+  CHECK_INNER(x); CHECK_INNER(out); CHECK_ALIGN16(x); CHECK_ALIGN16(code);
+  TORCH_CHECK(code.is_cuda() && is_fp8_code(code) && code.is_contiguous(), "gemm_w8: code [N, K] e4m3 contiguous");
+  const int M = x.size(0), K = x.size(1), N = code.size(0);
+  TORCH_CHECK(code.size(1) == K, "gemm_w8: K mismatch");
+  TORCH_CHECK(x.stride(0) % 8 == 0, "gemm_w8: x row stride % 8");
+  TORCH_CHECK(scale.is_cuda() && scale.scalar_type() == at::kFloat && scale.numel() == N && scale.is_contiguous(),
+              "gemm_w8: scale [N] f32");
+  CHECK_ALIGN16(scale);
+  TORCH_CHECK(epilogue == bfly::EPI_NONE || epilogue == bfly::EPI_SILU, "gemm_w8: epilogue none / silu");
+  const int nout = epilogue == bfly::EPI_SILU ? N / 2 : N;
+  TORCH_CHECK(out.is_cuda() && out.size(0) == M && out.size(1) == nout, "gemm_w8: out shape");
+  TORCH_CHECK(out.stride(0) % 4 == 0 && reinterpret_cast<uintptr_t>(out.data_ptr()) % 8 == 0,
+              "gemm_w8: out rows must be 8-B aligned");
+  float* ws = nullptr;
+  size_t ws_bytes = 0;
+  if (workspace.has_value()) {
+    TORCH_CHECK(workspace->is_cuda() && workspace->scalar_type() == at::kFloat && workspace->is_contiguous(),
+                "gemm_w8: workspace");
+    CHECK_ALIGN16(*workspace);
+    ws = workspace->data_ptr<float>();
+    ws_bytes = workspace->numel() * sizeof(float);
+  }
+  c10::DeviceGuard g(x.device());
+  const int rc = bfly::launch_gemm_w8(bf(x), x.stride(0), u8(code), scale.data_ptr<float>(), M, N, K, (int)epilogue,
+                                      bf(out), out.stride(0), ws, ws_bytes, cur_stream(), any_m, (int)force_sk);
+  TORCH_CHECK(rc == 0, "gemm_w8: shape / plan not taken by the native kernel M=", M, " N=", N, " K=", K,
+              " (rc=", rc, ")");
+}
+
 // 0 when the plan for (M, N, K, epilogue) has a packed-weight form (launch_gemm_packed dry run)
 int64_t gemm_packed_check(int64_t M, int64_t N, int64_t K, int64_t epilogue) {
   return bfly::launch_gemm_packed(nullptr, 0, nullptr, (int)M, (int)N, (int)K, (int)epilogue, nullptr, 0, nullptr,
@@ -1180,6 +1266,17 @@ TORCH_LIBRARY(bfly, m) {
   m.def("gemm_packed(Tensor x, Tensor wp, Tensor(a!) out, int epilogue, Tensor? ssp=None, float eps=0.0, "
         "Tensor? gates=None, int e0=0, int num_local=1, Tensor(b!)? workspace=None, bool defer=False) -> int");
   m.def("gemm_packed_check(int M, int N, int K, int epilogue) -> int", &gemm_packed_check);
+  m.def("quant_fp8_rows(Tensor w, Tensor(a!) code, Tensor(b!) scale) -> ()");
+  m.def("dequant_fp8(Tensor code, Tensor? scale, Tensor(a!) out) -> ()");
+  m.def("w8_scale_cols(Tensor y, Tensor scale, Tensor(a!) out, int epilogue) -> ()");
+  m.def("gemm_w8(Tensor x, Tensor code, Tensor scale, Tensor(a!) out, int epilogue, Tensor(b!)? workspace, "
+        "bool any_m=False, int force_sk=0) -> ()");
+  m.def("gemm_w8_check(int M, int N, int K, int epilogue) -> int",
+        [](int64_t M, int64_t N, int64_t K, int64_t e) -> int64_t { return bfly::gemm_w8_check(M, N, K, e); });
+  m.def("gemm_w8_splitk(int M, int N, int K, int epilogue) -> int",
+        [](int64_t M, int64_t N, int64_t K, int64_t e) -> int64_t { return bfly::gemm_w8_splitk(M, N, K, e); });
+  m.def("gemm_w8_workspace_size(int M, int N, int K) -> int",
+        [](int64_t M, int64_t N, int64_t K) -> int64_t { return (int64_t)bfly::gemm_w8_workspace_bytes(M, N, K); });
   m.def("gemm_with_plan(Tensor x, Tensor w, Tensor(a!) out, int[] plan, int epilogue, Tensor(b!)? workspace, "
         "Tensor? bias=None) -> ()");
   m.def("gemm_workspace_size(int M, int N, int K) -> int", &gemm_workspace_size);
@@ -1261,6 +1358,10 @@ TORCH_LIBRARY_IMPL(bfly, CUDA, m) {
   m.impl("gemm", &gemm);
   m.impl("gemm_silu_gate", &gemm_silu_gate);
   m.impl("gemm_packed", &gemm_packed);
+  m.impl("quant_fp8_rows", &quant_fp8_rows);
+  m.impl("dequant_fp8", &dequant_fp8);
+  m.impl("w8_scale_cols", &w8_scale_cols);
+  m.impl("gemm_w8", &gemm_w8);
   m.impl("gemm_with_plan", &gemm_with_plan);
   m.impl("gemm_deferred", &gemm_deferred);
   m.impl("splitk_reduce", &splitk_reduce);

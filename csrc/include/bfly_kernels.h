@@ -139,6 +139,30 @@ int launch_gemm_silu_gate(const bf16* X, long ldx, const bf16* W, long ldw, int 
                           bf16* out, long ldo, const float* gates, int gld, int ge0, int gF,
                           hipStream_t stream);
 
+// gemm_w8.hip: FP8 e4m3 weight-only linear layers (codes [N][K] row-major, one f32 scale per row)
+// code = RNE_e4m3fn(w / scale), scale = absmax(row) / 448 (1 for an all-zero row)
+void launch_quant_fp8_rows(const bf16* w, long ldw, long N, int K, uint8_t* code, float* scale,
+                           hipStream_t stream);
+// out[n][k] = bf16(float(code[n][k]) * scale[n]); scale == nullptr: the bare codes (exact)
+void launch_dequant_fp8(const uint8_t* code, const float* scale, long N, int K, bf16* out, long ldo,
+                        hipStream_t stream);
+// out = y[M][N] * scale[n] (EPI_NONE, in place allowed) or its SwiGLU [M][N/2] (EPI_SILU), y the
+// bf16 GEMM result over bare codes; N % 32 == 0
+void launch_w8_scale_cols(const bf16* y, long ldy, const float* scale, int M, int N, int epi, bf16* out,
+                          long ldo, hipStream_t stream);
+// 0 when the native kernel takes the shape (N % 128, K % 128, epilogue none / SiLU, M within
+// its row limit); ops.linear_w8 dequantises and runs the bf16 GEMM otherwise
+int gemm_w8_check(int M, int N, int K, int epi);
+int gemm_w8_splitk(int M, int N, int K, int epi);        // the native plan's split-K factor (0: none)
+size_t gemm_w8_workspace_bytes(int M, int N, int K);     // split-K slabs of the native plan
+// Y = scale[n] * (X . code^T), epilogue none / SiLU. `any_m`: run the native kernel above its
+// row limit too (64-row tiles, the weight re-streamed per tile), `force_sk`: another split-K
+// factor than the heuristic's (both for measurements; a forced split needs a workspace of
+// sk * M * N floats). < 0: not taken.
+int launch_gemm_w8(const bf16* X, long ldx, const uint8_t* W, const float* scale, int M, int N, int K,
+                   int epi, bf16* out, long ldo, float* ws, size_t ws_bytes, hipStream_t stream,
+                   bool any_m = false, int force_sk = 0);
+
 // attention.hip
 int attn_decode_splits(int max_ctx, int part_tokens);
 int attn_decode_part_tokens(int B, int Hkv, int max_ctx);

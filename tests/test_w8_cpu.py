@@ -1,0 +1,198 @@
+"""FP8 e4m3 weight-only quantisation on the CPU reference path: the format, the reference GEMM,
+the model / engine / tensor-parallel wiring and the refusals (GPU kernels: test_w8_gpu.py)."""
+import pytest
+import torch
+
+from butterfly_amd import ckpt, ops
+from butterfly_amd.config import EngineConfig, ModelConfig
+from butterfly_amd.engine.batch import make_decode_batch, make_prefill_batch
+from butterfly_amd.engine.engine import LLMEngine
+from butterfly_amd.engine.sampler import SamplingParams
+from butterfly_amd.models import Shard, build_model
+from butterfly_amd.ops import reference as ref
+from butterfly_amd.parallel.fake import FakeWorld
+from butterfly_amd.parallel.mesh import Mesh
+
+KINDS = ("qkv_w", "o_w", "gu_w", "down_w")
+# the prompts of tests/test_engine_gpu.py::test_prefill_and_decode_logits_match_reference
+LOGIT_PROMPTS = [[3, 1, 4, 1, 5, 9, 2, 6] * 9, list(range(1, 40)), [7]]
+GEN_PROMPTS = [[3, 14, 15, 92, 65], [35, 89, 79, 32, 38, 46, 26], [43], [38, 32, 79, 50, 28, 84]]
+
+
+def _rel(a, b):
+    a, b = a.float().cpu(), b.float().cpu()
+    return ((a - b).norm() / b.norm()).item()
+
+
+def test_format():
+    g = torch.Generator().manual_seed(0)
+    w = (torch.randn(256, 512, generator=g) * 0.05).to(torch.bfloat16)
+    w[17] = 0
+    code, scale = ref.quantize_fp8(w)
+    assert code.dtype == torch.float8_e4m3fn and code.shape == w.shape
+    assert scale.dtype == torch.float32 and scale.shape == (256,)
+    cf, wf = code.float(), w.float()
+    assert not torch.isnan(cf).any()
+    assert scale[17] == 1.0 and (cf[17] == 0).all()
+    live = torch.arange(256) != 17
+    idx = wf.abs().argmax(dim=1)
+    assert (cf[torch.arange(256), idx].abs()[live] == 448).all()
+    assert torch.equal(scale[live], wf.abs().amax(dim=1)[live] / 448)
+    # e4m3 half-ulp: 2^-4 relative for normals, half the subnormal step (2^-9 / 2) below them
+    err = (cf * scale[:, None] - wf).abs()
+    bound = torch.maximum(wf.abs() * 2.0 ** -4, scale[:, None] * 2.0 ** -10)
+    assert int((err > bound).sum()) == 0
+    assert torch.equal(ref.dequantize_fp8(code, scale, torch.float32), cf * scale[:, None])
+    assert torch.equal(ref.dequantize_fp8(code.view(torch.uint8), scale, torch.bfloat16),
+                       (cf * scale[:, None]).to(torch.bfloat16))
+    # the public op is the reference on the CPU
+    c2, s2 = ops.quantize_fp8(w)
+    assert torch.equal(c2.view(torch.uint8), code.view(torch.uint8)) and torch.equal(s2, scale)
+
+
+@pytest.mark.parametrize("epi", ["none", "silu"])
+def test_ref_linear_w8(epi):
+    g = torch.Generator().manual_seed(1)
+    x = torch.randn(37, 256, generator=g)
+    w = torch.randn(128, 256, generator=g) / 16 * torch.logspace(-6, 6, 128, base=2.0)[:, None]
+    code, scale = ref.quantize_fp8(w)
+    y = ref.linear_w8(x, code, scale, epilogue=epi)
+    want = x.float() @ (code.float() * scale[:, None]).t()
+    if epi == "silu":
+        gt, up = ref.split_gate_up(want, ref.SILU_INTERLEAVE)
+        want = torch.nn.functional.silu(gt) * up
+    assert y.shape == want.shape
+    assert _rel(y, want) < 1e-6
+    torch.testing.assert_close(y, want, rtol=1e-4, atol=1e-5 * float(want.abs().max()))
+    out = torch.empty_like(y)
+    assert ops.linear_w8(x, code, scale, epilogue=epi, out=out) is out and torch.equal(out, y)
+    with pytest.raises(ValueError):
+        ref.linear_w8(x, code, scale, epilogue="bias")
+
+
+def _twin(a, cfg, shard=Shard(), comm=None, seed=7):
+    """An ordinary model holding the dequantised values of quantised model `a`."""
+    b = build_model(cfg, shard, device="cpu", dtype=torch.float32, comm=comm)
+    b.init_random(seed)
+    for name, scale in a.wscale.items():
+        b.p[name].copy_(ref.dequantize_fp8(a.p[name], scale, torch.float32))
+    for name, t in a.p.items():
+        if name not in a.wscale:
+            assert torch.equal(t, b.p[name])
+    return b
+
+
+@pytest.mark.parametrize("preset", ["llama-tiny", "llama-small"])
+def test_model_wiring(preset):
+    cfg = ModelConfig.from_preset(preset)
+    a = build_model(cfg, device="cpu", dtype=torch.float32)
+    a.init_random(7)
+    full = a.local_bytes()
+    freed = a.quantize_weights("fp8")
+    assert a.weight_dtype == "fp8"
+    assert set(a.wscale) == {f"l{i}.{k}" for i in a.layer_ids for k in KINDS}
+    for name, s in a.wscale.items():
+        assert a.p[name].dtype == torch.float8_e4m3fn and s.dtype == torch.float32
+        assert s.shape == (a.p[name].shape[0],)
+    assert a.p["embed"].dtype == torch.float32 and a.head_weight.dtype == torch.float32
+    b = _twin(a, cfg)
+    assert a.local_bytes() < b.local_bytes() == full and freed == full - a.local_bytes()
+    assert a.gemm_shapes() == b.gemm_shapes()
+    bs = 32
+    tables, slots, nxt = [], [], 0
+    for p in LOGIT_PROMPTS:
+        nb = (len(p) + 8 + bs - 1) // bs
+        tables.append(list(range(nxt, nxt + nb)))
+        nxt += nb
+        slots.append([tables[-1][j // bs] * bs + j % bs for j in range(len(p))])
+    ka, kb = a.allocate_kv_cache(nxt + 1, bs), b.allocate_kv_cache(nxt + 1, bs)
+    fb = make_prefill_batch(LOGIT_PROMPTS, slots)
+    la, lb = a.forward(fb, ka), b.forward(fb, kb)
+    V = cfg.vocab_size
+    assert _rel(la[:, :V], lb[:, :V]) < 1e-5
+    toks = [int(t) for t in lb[:, :V].argmax(-1)]
+    pos = [len(p) for p in LOGIT_PROMPTS]
+    sl = [tables[i][pos[i] // bs] * bs + pos[i] % bs for i in range(len(LOGIT_PROMPTS))]
+    mb = max(len(t) for t in tables)
+    db = make_decode_batch(toks, pos, sl, tables, mb, mb * bs)
+    assert _rel(a.forward(db, ka)[:, :V], b.forward(db, kb)[:, :V]) < 1e-5
+
+
+def _ecfg(weight_dtype, **kw):
+    return EngineConfig(max_batch=8, max_seq_len=128, kv_cache_tokens=2048, use_graphs=False, seed=5,
+                        weight_dtype=weight_dtype, **kw)
+
+
+def _gen(eng, n=12):
+    return eng.generate(GEN_PROMPTS, SamplingParams(max_tokens=n, ignore_eos=True))
+
+
+def test_engine(monkeypatch):
+    monkeypatch.delenv("BFLY_WEIGHT_DTYPE", raising=False)
+    cfg = ModelConfig.from_preset("llama-tiny")
+    eng = LLMEngine(cfg, engine_cfg=_ecfg("fp8"), device="cpu")
+    assert eng.weight_dtype == "fp8" and eng.model.wscale
+    got = _gen(eng)
+    assert all(len(t) == 12 for t in got)
+    twin = _twin(eng.model, cfg, seed=5)
+    eng_b = LLMEngine(cfg, engine_cfg=_ecfg("bf16"), device="cpu", model=twin)
+    assert eng_b.weight_dtype == "bf16" and not eng_b.model.wscale
+    assert _gen(eng_b) == got
+    assert eng.model.local_bytes() < eng_b.model.local_bytes()
+    plain = LLMEngine(cfg, engine_cfg=_ecfg("auto"), device="cpu")
+    assert plain.weight_dtype == "bf16" and not plain.model.wscale
+    monkeypatch.setenv("BFLY_WEIGHT_DTYPE", "fp8")
+    flagged = LLMEngine(cfg, engine_cfg=_ecfg("auto"), device="cpu")
+    assert flagged.weight_dtype == "fp8" and _gen(flagged) == got
+    over = LLMEngine(cfg, engine_cfg=_ecfg("bf16"), device="cpu")
+    assert over.weight_dtype == "bf16" and not over.model.wscale
+    assert _gen(over) == _gen(plain)
+    with pytest.raises(ValueError, match="weight_dtype"):
+        LLMEngine(cfg, engine_cfg=_ecfg("int4"), device="cpu")
+
+
+def test_tensor_parallel():
+    """TP2: scales are per local shard row, so the reference ranks hold the dequantised values
+    of their OWN shards."""
+    torch.set_num_threads(1)
+    cfg = ModelConfig.from_preset("llama-tiny")
+    mesh = Mesh(tp=2)
+
+    def quantised(r, c):
+        eng = LLMEngine(cfg, mesh, _ecfg("fp8"), comm=c, device="cpu")
+        assert eng.model.wscale and eng.model.tp == 2
+        return _gen(eng)
+
+    def dequantised(r, c):
+        shard = Shard(tp_rank=mesh.coord(r).tp, tp_size=2, layer_start=0, layer_end=cfg.num_layers)
+        a = build_model(cfg, shard, device="cpu", dtype=torch.float32, comm=c)
+        a.init_random(5)
+        a.quantize_weights("fp8")
+        return _gen(LLMEngine(cfg, mesh, _ecfg("bf16"), comm=c, device="cpu", model=_twin(a, cfg, shard, c, seed=5)))
+
+    got = FakeWorld(mesh, timeout_s=120).run(quantised)
+    want = FakeWorld(mesh, timeout_s=120).run(dequantised)
+    assert got[0] == got[1] and all(len(t) == 12 for t in got[0])
+    assert got == want
+
+
+def test_refusals(tmp_path):
+    for preset, word in (("mixtral-tiny", "MoE"), ("gpt2-tiny", "bias")):
+        m = build_model(ModelConfig.from_preset(preset), device="cpu", dtype=torch.float32)
+        m.init_random(1)
+        with pytest.raises(ValueError, match=word):
+            m.quantize_weights("fp8")
+        assert not m.wscale
+        with pytest.raises(ValueError):
+            LLMEngine(ModelConfig.from_preset(preset), engine_cfg=_ecfg("fp8"), device="cpu")
+    cfg = ModelConfig.from_preset("llama-tiny")
+    m = build_model(cfg, device="cpu", dtype=torch.float32)
+    m.init_random(1)
+    with pytest.raises(ValueError):
+        m.quantize_weights("int4")
+    ckpt.save(m, tmp_path / "plain")
+    m.quantize_weights("fp8")
+    with pytest.raises(RuntimeError, match="quantis"):
+        ckpt.save(m, tmp_path / "quantised")
+    with pytest.raises(RuntimeError, match="quantis"):
+        ckpt.load_into(m, tmp_path / "plain")
