@@ -18,7 +18,7 @@ from .partition import Hardware, PartitionPlan, partition  # noqa: F401,E402
 
 
 def __getattr__(name):  # lazy: importing the engine pulls in the kernels / runtime
-    if name in ("LLM", "RequestOutput"):
+    if name in ("LLM", "RequestOutput", "TokenLogprob"):
         from . import api
 
         return getattr(api, name)

@@ -30,6 +30,17 @@ from .utils.tokenizer import load_tokenizer
 
 
 @dataclass
+class TokenLogprob:
+    """Log-probability of one generated token under log_softmax of the model's raw logits
+    (temperature, top-k and top-p do not enter), and the `SamplingParams.logprobs` most likely
+    tokens at that position as (token_id, logprob), most likely first (equal logits: lowest
+    token id first)."""
+    token_id: int
+    logprob: float
+    top: list = field(default_factory=list)
+
+
+@dataclass
 class RequestOutput:
     prompt: Union[str, list]
     token_ids: list
@@ -38,6 +49,19 @@ class RequestOutput:
     ttft_s: Optional[float] = None
     e2e_s: Optional[float] = None
     metrics: dict = field(default_factory=dict)
+    # SamplingParams.logprobs set: one TokenLogprob per generated token (None for a token
+    # generated before a resume: snapshots do not store logprobs), and the sum of the known ones
+    logprobs: Optional[list] = None
+    cumulative_logprob: Optional[float] = None
+
+
+def token_logprobs(req) -> tuple:
+    """(RequestOutput.logprobs, RequestOutput.cumulative_logprob) of an engine request."""
+    if req.params.logprobs is None:
+        return None, None
+    out = [None if e is None else TokenLogprob(int(t), float(e[0]), [(int(i), float(v)) for i, v in e[1]])
+           for t, e in zip(req.output, req.logprobs)]
+    return out, float(sum(e.logprob for e in out if e is not None))
 
 
 class LLM:
@@ -112,10 +136,12 @@ class LLM:
         for p, r in zip(mine, rids):
             req = eng.requests[r]
             text = self.tokenizer.decode(req.output) if isinstance(p, str) else None
+            lps, cum = token_logprobs(req)
             outs.append(RequestOutput(prompt=p, token_ids=list(req.output), text=text,
                                       finish_reason=req.finish_reason,
                                       ttft_s=(req.first_token_time - req.arrival) if req.first_token_time else None,
-                                      e2e_s=(req.finish_time or time.perf_counter()) - req.arrival))
+                                      e2e_s=(req.finish_time or time.perf_counter()) - req.arrival,
+                                      logprobs=lps, cumulative_logprob=cum))
         self.last_generate_s = time.perf_counter() - t0
         return outs
 
@@ -158,6 +184,8 @@ class LLM:
         outs = []
         for r in rids:
             req = eng.requests[r]
+            lps, cum = token_logprobs(req)
             outs.append(RequestOutput(prompt=req.prompt, token_ids=list(req.output),
-                                      text=self.tokenizer.decode(req.output), finish_reason=req.finish_reason))
+                                      text=self.tokenizer.decode(req.output), finish_reason=req.finish_reason,
+                                      logprobs=lps, cumulative_logprob=cum))
         return outs

@@ -2,7 +2,7 @@
 
   partition  --model llama3-70b --gpus 8 [--strategy tp2xpp4] [--objective latency] [--out plan.json]
              [--schedule RANK]   (that rank's decode-step communication program)
-  generate   --model llama-tiny|CKPT_DIR --prompt "..." [--max-tokens N] [--plan auto|tp2]
+  generate   --model llama-tiny|CKPT_DIR --prompt "..." [--max-tokens N] [--plan auto|tp2] [--logprobs N]
   serve      --model ... [--host 127.0.0.1 --port 8000]         (run under `launch` for N GPUs)
   bench      ...                                                  (forwards to bench.py)
   launch     -n 8 -- <program args...>                            one process per GPU
@@ -76,7 +76,8 @@ def cmd_generate(a) -> int:
                                          weight_dtype=a.weight_dtype),
               tokenizer=a.tokenizer)
     prompts = a.prompt or ["Hello"]
-    params = SamplingParams(max_tokens=a.max_tokens, temperature=a.temperature, seed=a.seed, ignore_eos=True)
+    params = SamplingParams(max_tokens=a.max_tokens, temperature=a.temperature, seed=a.seed, ignore_eos=True,
+                            logprobs=a.logprobs)
     # a restart is BFLY_RESTART (launch --max-restarts) or torchrun's TORCHELASTIC_RESTART_COUNT
     restart = max(int(os.environ.get("BFLY_RESTART", "0") or 0),
                   int(os.environ.get("TORCHELASTIC_RESTART_COUNT", "0") or 0))
@@ -101,6 +102,11 @@ def cmd_generate(a) -> int:
         for o in outs:
             print(json.dumps({"prompt": o.prompt, "text": o.text, "token_ids": o.token_ids,
                               "ttft_s": o.ttft_s, "e2e_s": o.e2e_s}))
+        for k, o in enumerate(outs):       # --logprobs: one line per generated token, after the text
+            for pos, e in enumerate(o.logprobs or []):
+                if e is not None:
+                    print(json.dumps({"request": k, "position": pos, "token_id": e.token_id, "logprob": e.logprob,
+                                      "top": [{"token_id": t, "logprob": v} for t, v in e.top]}))
     llm.close()
     return 0
 
@@ -200,6 +206,8 @@ def main(argv=None) -> int:
     g.add_argument("--plan", default="auto")
     g.add_argument("--tokenizer", default=None)
     g.add_argument("--no-graphs", action="store_true")
+    g.add_argument("--logprobs", type=int, default=None, metavar="N",
+                   help="print each generated token's log-probability and the N (0..20) most likely tokens")
     g.add_argument("--weight-dtype", default="auto", choices=["auto", "bf16", "fp8"],
                    help="dense projection weights: bf16, or fp8 (weight-only e4m3); auto = BFLY_WEIGHT_DTYPE")
     g.add_argument("--snapshot-dir", default=None,

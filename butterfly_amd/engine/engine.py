@@ -64,6 +64,9 @@ class Request:
     n_gen: int = 0                # tokens generated, including ones whose value is still in flight
     stopping: bool = False        # stop token seen while a plan holding the sequence is in flight
     sched_done: bool = False      # released from the scheduler
+    # params.logprobs set: one entry per token of `output`, (logprob, [(token id, logprob), ..])
+    # or None for a token generated before a resume (engine/state.py)
+    logprobs: list = field(default_factory=list)
 
     @property
     def tokens(self) -> list:
@@ -78,6 +81,8 @@ class StepOutput:
     finished: list
     seconds: float
     prefill_tokens: int = 0       # prompt tokens this step put through the model
+    logprobs: Optional[list] = None   # aligned with new_tokens (None: no row of the step asked);
+                                      # rows that did not ask hold None
 
 
 class LLMEngine:
@@ -207,12 +212,14 @@ class LLMEngine:
                              if self._prepost and self.device.type == "cuda" else None)
         d = self.model.dims
         self.sampler = Sampler(self.comm, cfg.vocab_size, d.vocab0, mesh.tp)
+        self._lp = None      # device logprobs of the rows just sampled (_sample), until applied
         if self.device.type == "cuda":
             ops.reserve_workspace(self.device, max_tokens=max(engine_cfg.max_prefill_tokens, engine_cfg.max_batch),
                                   max_n=self._max_gemm_n(), max_k=self._max_gemm_k(),
                                   max_batch=max(engine_cfg.graph_batch_sizes + [engine_cfg.max_batch]),
                                   max_ctx=engine_cfg.max_seq_len, num_kv_heads=d.hkv, head_dim=cfg.head_dim,
-                                  shapes=self.model.gemm_shapes(), w8_shapes=self.model.w8_shapes())
+                                  shapes=self.model.gemm_shapes(), w8_shapes=self.model.w8_shapes(),
+                                  vocab=min(d.vocab, max(0, cfg.vocab_size - d.vocab0)))
         buckets = [b for b in engine_cfg.graph_batch_sizes if b <= engine_cfg.max_batch] or [engine_cfg.max_batch]
         if self.async_pp and self.scheduler.group_batch not in buckets:
             buckets.append(self.scheduler.group_batch)    # a full group replays one graph
@@ -307,6 +314,7 @@ class LLMEngine:
         params = params or SamplingParams()
         if len(prompt) + params.max_tokens > self.ecfg.max_seq_len:
             raise ValueError(f"prompt ({len(prompt)}) + max_tokens ({params.max_tokens}) exceeds max_seq_len")
+        self._check_logprobs(params)
         self.requests[rid] = Request(rid, list(prompt), params, arrival=time.perf_counter())
         if self.cp_min and len(prompt) >= self.cp_min:
             self._cp_queue.append(rid)        # prefilled by the DP group together (_cp_step)
@@ -316,9 +324,20 @@ class LLMEngine:
             self.scheduler.add(rid, len(prompt), params.max_tokens)
         return rid
 
+    def _check_logprobs(self, params: SamplingParams) -> None:
+        n = params.logprobs
+        if n is None:
+            return
+        if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= ops.LOGPROBS_MAX_N:
+            raise ValueError(f"logprobs must be None or an integer in 0..{ops.LOGPROBS_MAX_N}, got {n!r}")
+        if self.mesh.pp > 1:
+            # only the last stage holds logits; a second boundary broadcast is not built
+            raise ValueError("logprobs is not supported with pipeline parallelism (pp > 1)")
+
     def _admit_resumed(self, req: Request) -> None:
         """Scheduler admission of a restored request (engine/state.py): its prompt plus the
         tokens it already generated are prefilled as one sequence, the rest is generated."""
+        self._check_logprobs(req.params)
         toks = req.tokens
         remaining = req.params.max_tokens - len(req.output)
         if len(toks) + remaining > self.ecfg.max_seq_len:
@@ -385,9 +404,45 @@ class LLMEngine:
         return temps, seeds, any(q.params.needs_filter for q in reqs)
 
     def _sample(self, logits: torch.Tensor, rids: list, graph_ids=None) -> torch.Tensor:
+        """One token id per row (`graph_ids`: already sampled by the decode graph). When some
+        row's request asks for logprobs they are computed here, eagerly, from the same logits
+        (the graph's static output on the graph-sampling path) and left in `_lp` for whoever
+        applies the ids; a step in which no row asks launches nothing more."""
         if graph_ids is not None and not self._poison:
-            return graph_ids
-        return self._sample_eager(logits, rids)
+            ids = graph_ids
+        else:
+            ids = self._sample_eager(logits, rids)
+        self._lp = self._logprobs(logits, rids, ids)
+        return ids
+
+    def _logprobs(self, logits: torch.Tensor, rids: list, ids: torch.Tensor) -> Optional[tuple]:
+        """(chosen_lp [R], top_ids [R, n], top_lp [R, n]) on the device for the largest n some
+        row of the step asks for (sliced per request on the host), or None if none asks."""
+        ns = [self.requests[r].params.logprobs for r in rids]
+        ns = [n for n in ns if n is not None]
+        if not ns:
+            return None
+        return self.sampler.logprobs(logits, ids, max(ns))
+
+    def _take_lp(self) -> Optional[tuple]:
+        lp, self._lp = self._lp, None
+        return lp
+
+    def _lp_entries(self, rids: list, lp: Optional[tuple]) -> Optional[list]:
+        """Host entries of a step's logprob tensors (device, or their pinned copies): per row
+        (logprob, [(token id, logprob), ...]) cut to the request's own n, None if it did not
+        ask. Missing alternatives (id -1) are dropped."""
+        if lp is None:
+            return None
+        if any(t.is_cuda for t in lp):
+            lp = ops.logprobs_to_host(lp)        # synchronous engine: with the ids, one copy
+        chosen, top_ids, top_lp = (t.tolist() for t in lp)
+        out = []
+        for i, r in enumerate(rids):
+            n = self.requests[r].params.logprobs
+            out.append(None if n is None else
+                       (chosen[i], [(t, v) for t, v in zip(top_ids[i][:n], top_lp[i][:n]) if t >= 0]))
+        return out
 
     def _sample_eager(self, logits: torch.Tensor, rids: list) -> torch.Tensor:
         """Sample one token per row. With BFLY_NAN_CHECK the sampling kernel also flags rows
@@ -514,11 +569,15 @@ class LLMEngine:
         """Append one sampled token per sequence, retire finished ones, record metrics."""
         finished = []
         now = time.perf_counter()
+        lp = self._take_lp()
         if any(int(t) < 0 for t in new):
             raise RuntimeError(f"rank {self.rank}: non-finite logits at engine step {self.steps_done}")
-        for r, t in zip(rids, new):
+        lps = self._lp_entries(rids, lp)      # to the host with the ids
+        for i, (r, t) in enumerate(zip(rids, new)):
             req = self.requests[r]
             req.output.append(int(t))
+            if lps is not None and lps[i] is not None:
+                req.logprobs.append(lps[i])
             req.n_gen = len(req.output)
             if req.first_token_time is None:
                 req.first_token_time = now
@@ -535,7 +594,7 @@ class LLMEngine:
                 finished.append(r)
         dt = time.perf_counter() - t0
         self.metrics.observe_step(kind, len(rids), dt)
-        return StepOutput(kind, rids, new, finished, dt)
+        return StepOutput(kind, rids, new, finished, dt, logprobs=lps)
 
     def _ep_agree(self, plan) -> tuple:
         """Expert-parallel step agreement (host integers over the control plane, no device
@@ -768,10 +827,14 @@ class LLMEngine:
             if leaving.ids.is_cuda:
                 leaving.host = torch.empty(len(leaving.rids), dtype=torch.int32, pin_memory=True)
                 leaving.host.copy_(leaving.ids, non_blocking=True)
+                if leaving.lp is not None:     # its logprobs travel with the ids, under the same event
+                    leaving.lp_host = ops.logprobs_to_host(leaving.lp, non_blocking=True)
                 leaving.event = torch.cuda.Event()
                 leaving.event.record()
             else:
                 leaving.host = leaving.ids
+                leaving.lp_host = leaving.lp
+            leaving.lp = None
             self._pending = leaving
         if self._prepost:
             self._prepost_recv(k + 1 - s)
@@ -833,17 +896,22 @@ class LLMEngine:
         if any(t < 0 for t in new):
             raise RuntimeError(f"rank {self.rank}: non-finite logits at engine step {self.steps_done}")
         now = time.perf_counter()
-        rids, toks, finished = [], [], []
+        lps = self._lp_entries(p.rids, p.lp_host)
+        rids, toks, finished, kept = [], [], [], []
         inflight = {r for q in self._inflight for r in q.seqs}
         if self._pending is not None:
             inflight.update(self._pending.seqs)
-        for r, t in zip(p.rids, new):
+        for i, (r, t) in enumerate(zip(p.rids, new)):
             req = self.requests[r]
             if req.finished:
-                continue                      # a token after the stop token: discarded
+                continue                      # a token after the stop token: discarded, with its logprobs
             req.output.append(t)
             rids.append(r)
             toks.append(t)
+            if lps is not None:
+                kept.append(lps[i])
+                if lps[i] is not None:
+                    req.logprobs.append(lps[i])
             if req.first_token_time is None:
                 req.first_token_time = now
             stop = not req.params.ignore_eos and (t in req.params.stop_token_ids or
@@ -860,7 +928,7 @@ class LLMEngine:
                         self.scheduler.finish(r)
         dt = time.perf_counter() - t0
         self.metrics.observe_step(p.kind, len(rids), dt)
-        return StepOutput(p.kind, rids, toks, finished, dt)
+        return StepOutput(p.kind, rids, toks, finished, dt, logprobs=kept if lps is not None else None)
 
     def _first_stage_ids(self, p: PipePlan, rids: Optional[list] = None):
         """Input ids of the decode rows (`rids`, default the plan's) of a plan entering stage
@@ -985,6 +1053,7 @@ class LLMEngine:
             graph_ids = self.runner.last_ids if (p.plan.kind == 2 and not state.get("filtered")) else None
             p.ids = self._sample(out, p.rids, graph_ids) if p.rids else \
                 torch.empty(0, dtype=torch.int32, device=self.device)
+            p.lp = self._take_lp()
 
         self._execute(self._ops(1, native_dec), recv, run, send, sample)
 

@@ -110,6 +110,8 @@ class PipePlan:
     ids: Optional[object] = None   # sampled ids tensor (last stage / after broadcast)
     host: Optional[object] = None  # pinned host copy of `ids` (async D2H at broadcast time)
     event: Optional[object] = None # marks that copy complete
+    lp: Optional[tuple] = None      # device logprobs of the sampled rows (Sampler.logprobs), if asked
+    lp_host: Optional[tuple] = None # their pinned host copies, made with `host` under `event`
 
     @property
     def kind(self) -> str:

@@ -35,6 +35,7 @@ class SamplingParams:
     stop_token_ids: list = field(default_factory=list)
     ignore_eos: bool = False
     seed: Optional[int] = None
+    logprobs: Optional[int] = None    # None = off; 0 = the generated token's; N = also the N most likely
 
     @property
     def needs_filter(self) -> bool:
@@ -66,6 +67,20 @@ class Sampler:
         if self.tp == 1:
             return ids
         return self._merge(ids, scores)
+
+    def logprobs(self, logits: torch.Tensor, ids: torch.Tensor, n: int) -> tuple:
+        """Log-probabilities under log_softmax of the raw logits over the whole vocabulary
+        (temperature and filters do not enter): (chosen_lp [R] f32 of the global ids `ids`,
+        top_ids [R, n] int32, top_lp [R, n] f32: the n most likely tokens, logit descending,
+        token id ascending on ties; id -1 / -inf where fewer than n tokens exist). One fused
+        pass over this rank's shard (ops.logprobs_partial) and, under TP, one all-gather of the
+        [R, 3 + 2n] f32 records; identical on every TP rank. Issued eagerly, like the top-k /
+        top-p all-reduces, outside the runner's checked stage program."""
+        rec = ops.logprobs_partial(self._local_valid(logits), ids, n, vstart=self.vocab_start)
+        if self.tp == 1:
+            return ops.logprobs_merge(rec.view(1, *rec.shape))
+        allr = self.comm.all_gather(rec, "tp").view(self.tp, rec.shape[0], rec.shape[1])
+        return ops.logprobs_merge(allr)
 
     def _merge(self, ids: torch.Tensor, scores: torch.Tensor) -> torch.Tensor:
         """Each vocab shard's winner -> the global winner: (score, id) pairs all-gathered over

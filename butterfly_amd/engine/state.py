@@ -19,7 +19,9 @@ replayed (cli.py `generate`).
 
 Format `butterfly-engine-state` v1 (JSON): {"format", "version", "model", "job", "dp_rank", "dp_size",
 "next_id", "steps_done", "requests": [{"rid", "prompt", "output", "params", "finished",
-"finish_reason"}]}. Tokens still in flight in the asynchronous pipeline (sampled, value not yet
+"finish_reason"}]}. `params` may lack fields added later (`logprobs`: absent = off); the
+log-probabilities themselves are not stored, so tokens generated before the snapshot report None
+after a resume. Tokens still in flight in the asynchronous pipeline (sampled, value not yet
 on the host) are not part of it: they are recomputed after the resume.
 
 Periodic snapshots: EngineConfig.snapshot_dir + snapshot_every (steps); one rank per replica (tp 0,
@@ -89,6 +91,8 @@ def restore(engine, state: dict, job: Optional[str] = None) -> list:
             req = Request(rid, prompt, params, output=output, n_gen=len(output), finished=done,
                           finish_reason=r.get("finish_reason") or ("length" if done else None),
                           sched_done=done)
+            if params.logprobs is not None:
+                req.logprobs = [None] * len(output)     # logprobs are not stored in snapshots
             engine.requests[rid] = req
             if not done:
                 engine._admit_resumed(req)

@@ -199,13 +199,14 @@ def reserve_w8_workspace(device, max_tokens: int, w8_shapes) -> None:
 
 def reserve_workspace(device, max_tokens: int, max_n: int, max_k: int, max_batch: int = 0,
                       max_ctx: int = 0, num_kv_heads: int = 0, head_dim: int = 128, shapes=(),
-                      w8_shapes=()) -> None:
+                      w8_shapes=(), vocab: int = 0) -> None:
     """Pre-size every workspace for problems up to the given bounds (call before capture).
     `shapes`: the model's GEMM weight shapes (N, K); the split-K slab need is the max over them
     and every token-count bucket of the plan table (a tuned plan may split a small projection
     more than the largest one is split). `w8_shapes`: the (N, K) of FP8-quantised projections:
     sizes the native FP8 GEMM's split-K slabs and, for token counts (or shapes) that take the
-    dequantise route, the bf16 scratch of the largest of them."""
+    dequantise route, the bf16 scratch of the largest of them. `vocab`: columns of the logits
+    shard; sizes the logprobs partials for `max_batch` rows with the most alternatives."""
     if not load_library():
         return
     reserve_w8_workspace(device, max_tokens, w8_shapes)
@@ -224,6 +225,9 @@ def reserve_workspace(device, max_tokens: int, max_n: int, max_k: int, max_batch
         _arena.get(device, "attn_ml", max_batch * num_kv_heads * ns * 16 * 2, torch.float32)
     _arena.get(device, "sample", max(max_batch, max_tokens, 1) * 64, torch.int64)
     _arena.get(device, "tkp", max(max_batch, max_tokens, 1) * 521, torch.float32)
+    if vocab:
+        _arena.get(device, "logprobs", torch.ops.bfly.logprobs_workspace_size(max(max_batch, 1), vocab, LOGPROBS_MAX_N),
+                   torch.int64)
 
 
 # ---------------------------------------------------------------------------------------
@@ -444,6 +448,69 @@ def sample(logits, temps=None, seeds=None, vstart: int = 0, out_ids=None, out_sc
     ws = _arena.get(logits.device, "sample", rows * 64, torch.int64)
     torch.ops.bfly.sample(logits, temps, seeds, vstart, out_ids, out_scores, ws, thresh, check_finite)
     return out_ids, out_scores
+
+
+LOGPROBS_MAX_N = 20
+
+
+def logprobs_partial(logits, ids, n: int, vstart: int = 0):
+    """One vocab shard's logprob record [R, 3 + 2n] f32 (logprobs.hip; layout in
+    ops.reference.logprobs_partial): the shard's log-softmax statistics, the logit of the chosen
+    global id `ids[r]` (int32; -inf when it lies outside the shard) and the shard's `n` (0..20)
+    largest logits with their global ids. `logits`: bf16 [R, V_local], a column slice of the
+    padded logits is fine (row stride a multiple of 8)."""
+    n = int(n)
+    if not 0 <= n <= LOGPROBS_MAX_N:
+        raise ValueError(f"logprobs: n must be in 0..{LOGPROBS_MAX_N}, got {n}")
+    if not _gpu(logits):
+        return ref.logprobs_partial(logits, ids, n, vstart)
+    R, V = logits.shape
+    rec = _empty(R, 3 + 2 * n, dtype=torch.float32, device=logits.device)
+    ws = _arena.get(logits.device, "logprobs", torch.ops.bfly.logprobs_workspace_size(R, V, n), torch.int64)
+    torch.ops.bfly.logprobs_partial(logits, ids.contiguous(), n, int(vstart), rec, ws)
+    return rec
+
+
+def logprobs_merge(records):
+    """Shard records [tp, R, 3 + 2n] (tp = 1 too) -> (chosen_lp [R] f32, top_ids [R, n] int32,
+    top_lp [R, n] f32): log_softmax over the whole vocabulary at the chosen token and at the n
+    most likely ones (logit descending, global id ascending on ties; id -1 / -inf = none)."""
+    if not _gpu(records):
+        return ref.logprobs_merge(records)
+    _, R, L = records.shape
+    n = (L - 3) // 2
+    # one buffer of 4-byte words behind the three outputs, so they reach the host in one copy
+    packed = _empty(R * (1 + 2 * n), dtype=torch.float32, device=records.device)
+    chosen, top_ids, top_lp = _logprobs_views(packed, R, n)
+    torch.ops.bfly.logprobs_merge(records.contiguous(), chosen, top_ids, top_lp)
+    return Logprobs(chosen, top_ids, top_lp, packed)
+
+
+class Logprobs(tuple):
+    """(chosen_lp, top_ids, top_lp) of `logprobs_merge`; `packed`: the one f32 buffer the three
+    are views of (None on the reference path)."""
+
+    def __new__(cls, chosen, top_ids, top_lp, packed=None):
+        self = super().__new__(cls, (chosen, top_ids, top_lp))
+        self.packed = packed
+        return self
+
+
+def _logprobs_views(packed, R: int, n: int):
+    return (packed[:R], packed[R + R * n:].view(torch.int32).view(R, n), packed[R:R + R * n].view(R, n))
+
+
+def logprobs_to_host(lp, non_blocking: bool = False):
+    """Host copies of a `logprobs_merge` result: GPU results travel as one copy of their shared
+    buffer, into pinned memory and asynchronous on the current stream when `non_blocking` (the
+    caller orders its reads with an event)."""
+    packed = getattr(lp, "packed", None)
+    if packed is None or not packed.is_cuda:
+        return tuple(t.cpu() for t in lp)
+    R, n = lp[1].shape
+    host = torch.empty(packed.shape, dtype=packed.dtype, pin_memory=non_blocking)
+    host.copy_(packed, non_blocking=non_blocking)
+    return _logprobs_views(host, R, n)
 
 
 def topkp_threshold(logits, temps, top_k, top_p, reduce_sum=None, reduce_max=None,

@@ -88,6 +88,61 @@ def sample_merge(allp):
     return allp.gather(0, best.view(1, -1, 1).expand(1, -1, 2))[0, :, 1].to(torch.int32)
 
 
+def logprobs_partial(logits, ids, n, vstart=0):
+    """One vocab shard's logprob record [R, 3 + 2n] f32 (logprobs.hip): (row max M,
+    sum exp(x - M), logit of ids[r] or -inf when it lies outside the shard, n x (logit, global
+    id) of the shard's n largest logits: logit descending, global id ascending on ties; missing
+    entries (-inf, -1)). A -inf logit carries no mass; an all -inf (or empty) shard has S = 0."""
+    lf = logits.float()
+    R, V = lf.shape
+    n = int(n)
+    rec = torch.empty(R, 3 + 2 * n, dtype=torch.float32, device=lf.device)
+    M = lf.max(1).values if V else torch.full((R,), float("-inf"), device=lf.device)
+    finite = torch.isfinite(M) if V else torch.zeros(R, dtype=torch.bool, device=lf.device)
+    rec[:, 0] = M
+    rec[:, 1] = torch.where(finite, torch.exp(lf - torch.where(finite, M, torch.zeros_like(M)).view(R, 1)).sum(1),
+                            torch.zeros_like(M)) if V else 0.0
+    lid = ids.to(torch.int64) - int(vstart)
+    inside = (lid >= 0) & (lid < V)
+    ch = lf.gather(1, lid.clamp(0, max(V - 1, 0)).view(R, 1)).view(R) if V else torch.zeros(R, device=lf.device)
+    rec[:, 2] = torch.where(inside, ch, torch.full_like(M, float("-inf")))
+    k = min(n, V)
+    rec[:, 3::2] = float("-inf")
+    rec[:, 4::2] = -1.0
+    if k:
+        val, idx = torch.sort(lf, dim=1, descending=True, stable=True)   # ties: lowest index first
+        rec[:, 3:3 + 2 * k:2] = val[:, :k]
+        rec[:, 4:4 + 2 * k:2] = (idx[:, :k] + int(vstart)).float()
+    return rec
+
+
+def logprobs_merge(records):
+    """Shard records [tp, R, 3 + 2n] -> (chosen_lp [R] f32, top_ids [R, n] int32, top_lp [R, n]
+    f32): log_softmax over the union of the shards at the chosen token and at the n largest
+    logits (descending; smallest global id first on ties; missing entries id -1, logprob -inf)."""
+    rec = records.float()
+    tp, R, L = rec.shape
+    n = (L - 3) // 2
+    m, s = rec[:, :, 0], rec[:, :, 1]
+    M = m.max(0).values
+    w = torch.where(torch.isfinite(m), torch.exp(m - torch.where(torch.isfinite(M), M, torch.zeros_like(M))),
+                    torch.zeros_like(m))
+    lse = M + torch.log((s * w).sum(0))
+    chosen = rec[:, :, 2].max(0).values - lse
+    val = rec[:, :, 3::2].permute(1, 0, 2).reshape(R, tp * n)
+    gid = rec[:, :, 4::2].permute(1, 0, 2).reshape(R, tp * n).to(torch.int64)
+    # order by (logit descending, id ascending): sort by id first, then stably by logit;
+    # missing entries (id -1) go last
+    val = torch.where(gid >= 0, val, torch.full_like(val, float("-inf")))
+    big = torch.where(gid >= 0, gid, torch.full_like(gid, 1 << 40))
+    o1 = torch.sort(big, dim=1, stable=True).indices
+    val, gid = val.gather(1, o1), gid.gather(1, o1)
+    o2 = torch.sort(val, dim=1, descending=True, stable=True).indices[:, :n]
+    top_v, top_i = val.gather(1, o2), gid.gather(1, o2)
+    top_lp = torch.where(top_i >= 0, top_v - lse.view(R, 1), torch.full_like(top_v, float("-inf")))
+    return chosen, top_i.to(torch.int32), top_lp
+
+
 def gather_rows(src, idx, out):
     """out[i] = src[idx[i]] where idx[i] >= 0; other rows of `out` are left as they are."""
     ok = idx >= 0

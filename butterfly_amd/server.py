@@ -12,11 +12,17 @@ Streaming (`"stream": true`, OpenAI server-sent events): the stream flag travels
 request broadcast, so each replica's leader also reports the tokens its streaming requests
 gained in the step; rank 0 pushes them into the request's queue and the HTTP handler emits one
 `data:` event per token, then a final event with the finish reason and `data: [DONE]`.
+
+Logprobs (`"logprobs": N`, 0..20): the response's choice gains `logprobs` = {"token_ids",
+"token_logprobs", "top_logprobs": [[{"token_id", "logprob", "token"}]]} (log_softmax of the raw
+logits; `token` is the decoded piece for text prompts, else null); with streaming each token
+event carries its own entry. Responses to requests without the field are unchanged.
 """
 from __future__ import annotations
 
 import asyncio
 import itertools
+import math
 import queue
 import threading
 import time
@@ -39,7 +45,7 @@ class ServingLoop:
         self.inbox: "queue.Queue" = queue.Queue()
         self.waiters: dict = {}
         self.results: dict = {}
-        self.streams: dict = {}          # rank 0: gid -> queue of ("token", id) / ("done", result)
+        self.streams: dict = {}          # rank 0: gid -> queue of ("token", (id, logprob entry)) / ("done", result)
         self.streaming: set = set()      # every rank: gids whose tokens are reported per step
         self.idle_sleep = idle_sleep
         self.stop = False
@@ -58,7 +64,8 @@ class ServingLoop:
         return gid
 
     def stream_events(self, gid: int, timeout: float = 600.0):
-        """Blocking iterator over ("token", id) ... ("done", result) for a streaming request."""
+        """Blocking iterator over ("token", (id, logprob entry or None)) ... ("done", result) for a
+        streaming request."""
         q = self.streams[gid]
         try:
             while True:
@@ -110,11 +117,13 @@ class ServingLoop:
             if eng.has_unfinished() or eng.lockstep_dp:
                 out = eng.step()
                 if self.streaming:
-                    tokens = [(r, t) for r, t in zip(out.rids, out.new_tokens) if r in self.streaming]
+                    lps = out.logprobs or [None] * len(out.rids)
+                    tokens = [(r, t, e) for r, t, e in zip(out.rids, out.new_tokens, lps) if r in self.streaming]
                 for rid in out.finished:
                     self.streaming.discard(rid)
                     req = eng.requests.pop(rid)
                     finished.append((rid, {"token_ids": list(req.output), "finish_reason": req.finish_reason,
+                                           "logprobs": list(req.logprobs) if req.params.logprobs is not None else None,
                                            "ttft_s": req.first_token_time - req.arrival if req.first_token_time else None,
                                            "e2e_s": req.finish_time - req.arrival}))
             elif not new:
@@ -126,10 +135,10 @@ class ServingLoop:
                     finished = [x for f, _ in got for x in f]
                     tokens = [x for _, t in got for x in t]
             if self.rank == 0:
-                for rid, tok in tokens:
+                for rid, tok, lp in tokens:
                     q = self.streams.get(rid)
                     if q is not None:
-                        q.put(("token", int(tok)))
+                        q.put(("token", (int(tok), lp)))
                 for rid, res in finished:
                     self._publish(rid, res)
 
@@ -156,8 +165,8 @@ def _request_model(BaseModel):
     # built at runtime (pydantic is imported lazily); annotations are real types, not strings
     ns = {"__annotations__": {"model": Optional[str], "prompt": object, "max_tokens": int, "temperature": float,
                               "top_p": float, "top_k": int, "seed": Optional[int], "stop_token_ids": list,
-                              "stream": bool},
-          "model": None, "max_tokens": 16, "temperature": 0.0, "top_p": 1.0, "top_k": 0, "seed": None,
+                              "stream": bool, "logprobs": Optional[int]},
+          "logprobs": None, "model": None, "max_tokens": 16, "temperature": 0.0, "top_p": 1.0, "top_k": 0, "seed": None,
           "stop_token_ids": [], "stream": False}
     return type("CompletionRequest", (BaseModel,), ns)
 
@@ -187,6 +196,16 @@ def create_app(loop: ServingLoop):
     def metrics():
         return loop.engine.metrics.to_prometheus()
 
+    def logprobs_json(token_ids, entries, is_text):
+        """The `logprobs` object of a choice for `token_ids` and their engine entries."""
+        piece = (lambda t: tok.decode([t])) if is_text else (lambda t: None)
+        num = lambda v: v if math.isfinite(v) else None     # noqa: E731 (JSON has no -inf: a masked token)
+        return {"token_ids": list(token_ids),
+                "token_logprobs": [None if e is None else num(e[0]) for e in entries],
+                "top_logprobs": [None if e is None else
+                                 [{"token_id": int(t), "logprob": num(v), "token": piece(int(t))} for t, v in e[1]]
+                                 for e in entries]}
+
     async def completions(req):
         if isinstance(req.prompt, str):
             ids, is_text = tok.encode(req.prompt), True
@@ -194,16 +213,22 @@ def create_app(loop: ServingLoop):
             ids, is_text = req.prompt, False
         else:
             raise HTTPException(400, "prompt must be a string or a list of token ids")
+        if req.logprobs is not None and not 0 <= req.logprobs <= 20:
+            raise HTTPException(400, "logprobs must be an integer in 0..20")
         params = SamplingParams(max_tokens=req.max_tokens, temperature=req.temperature, top_p=req.top_p,
-                                top_k=req.top_k, seed=req.seed, stop_token_ids=req.stop_token_ids)
+                                top_k=req.top_k, seed=req.seed, stop_token_ids=req.stop_token_ids,
+                                logprobs=req.logprobs)
         if req.stream:
             gid = loop.submit(ids, params, stream=True)
 
             def sse():   # runs in Starlette's threadpool: the blocking queue reads are fine
                 for kind, val in loop.stream_events(gid):
                     if kind == "token":
+                        val, lp = val
                         chunk = {"index": 0, "token_ids": [val], "text": tok.decode([val]) if is_text else None,
                                  "finish_reason": None}
+                        if params.logprobs is not None:
+                            chunk["logprobs"] = logprobs_json([val], [lp], is_text)
                     else:
                         chunk = {"index": 0, "token_ids": [], "text": "" if is_text else None,
                                  "finish_reason": val["finish_reason"]}
@@ -216,9 +241,11 @@ def create_app(loop: ServingLoop):
         gid = loop.submit(ids, params)
         res = await asyncio.get_running_loop().run_in_executor(None, loop.wait, gid, 600.0)
         text = tok.decode(res["token_ids"]) if is_text else None
+        choice = {"index": 0, "text": text, "token_ids": res["token_ids"], "finish_reason": res["finish_reason"]}
+        if res.get("logprobs") is not None:
+            choice["logprobs"] = logprobs_json(res["token_ids"], res["logprobs"], is_text)
         return {"id": f"cmpl-{gid}", "object": "text_completion", "model": loop.llm.cfg.name,
-                "choices": [{"index": 0, "text": text, "token_ids": res["token_ids"],
-                             "finish_reason": res["finish_reason"]}],
+                "choices": [choice],
                 "usage": {"prompt_tokens": len(ids), "completion_tokens": len(res["token_ids"])},
                 "timing": {"ttft_s": res["ttft_s"], "e2e_s": res["e2e_s"]}}
 

@@ -279,6 +279,48 @@ void sample(const Tensor& logits, const c10::optional<Tensor>& temps,
                       out_scores.data_ptr<float>(), cur_stream(), thp, check_finite ? 1 : 0);
 }
 
+// Per-token logprobs (logprobs.hip): one shard's record [rows, 3 + 2n] f32.
+int64_t logprobs_workspace_size(int64_t rows, int64_t V, int64_t n) {
+  return (int64_t)bfly::logprobs_workspace_words(rows, (int)V, (int)n);
+}
+
+void logprobs_partial(const Tensor& logits, const Tensor& ids, int64_t n, int64_t vstart, Tensor& record,
+                      Tensor& workspace) {
+  CHECK_GPU(logits); CHECK_BF16(logits); CHECK_GPU(ids); CHECK_I32(ids); CHECK_GPU(record); CHECK_GPU(workspace);
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && logits.stride(0) % 8 == 0, "logprobs_partial: logits");
+  CHECK_ALIGN16(logits);
+  const int64_t rows = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(n >= 0 && n <= bfly::kLogprobsMaxN, "logprobs_partial: n must be in 0..", bfly::kLogprobsMaxN);
+  TORCH_CHECK(V <= (int64_t)bfly::kLogprobsChunk * bfly::kLogprobsMaxChunks, "logprobs_partial: at most ",
+              bfly::kLogprobsChunk * bfly::kLogprobsMaxChunks, " columns");
+  TORCH_CHECK(vstart >= 0 && vstart + V < (1ll << 24), "logprobs_partial: token ids must stay below 2^24");
+  TORCH_CHECK(ids.is_contiguous() && ids.numel() == rows, "logprobs_partial: ids [rows] int32");
+  TORCH_CHECK(record.scalar_type() == at::kFloat && record.is_contiguous() && record.dim() == 2 &&
+                  record.size(0) == rows && record.size(1) == 3 + 2 * n, "logprobs_partial: record [rows, 3 + 2n] f32");
+  TORCH_CHECK(workspace.scalar_type() == at::kLong && workspace.is_contiguous() &&
+                  workspace.numel() >= logprobs_workspace_size(rows, V, n), "logprobs_partial: workspace");
+  c10::DeviceGuard g(logits.device());
+  bfly::launch_logprobs_partial(bf(logits), logits.stride(0), rows, V, vstart, ids.data_ptr<int>(), n,
+                                reinterpret_cast<uint64_t*>(workspace.data_ptr()), record.data_ptr<float>(),
+                                cur_stream());
+}
+
+void logprobs_merge(const Tensor& records, Tensor& chosen_lp, Tensor& top_ids, Tensor& top_lp) {
+  CHECK_GPU(records); CHECK_GPU(chosen_lp); CHECK_GPU(top_ids); CHECK_GPU(top_lp); CHECK_I32(top_ids);
+  TORCH_CHECK(records.scalar_type() == at::kFloat && records.is_contiguous() && records.dim() == 3 &&
+                  records.size(2) >= 3 && (records.size(2) - 3) % 2 == 0, "logprobs_merge: records [tp, rows, 3 + 2n] f32");
+  const int64_t tp = records.size(0), rows = records.size(1), n = (records.size(2) - 3) / 2;
+  TORCH_CHECK(tp >= 1 && n <= bfly::kLogprobsMaxN && tp * n <= bfly::kLogprobsMaxChunks * bfly::kLogprobsMaxN,
+              "logprobs_merge: tp >= 1, n <= ", bfly::kLogprobsMaxN, ", tp * n <= ",
+              bfly::kLogprobsMaxChunks * bfly::kLogprobsMaxN);
+  TORCH_CHECK(chosen_lp.scalar_type() == at::kFloat && chosen_lp.is_contiguous() && chosen_lp.numel() == rows &&
+                  top_lp.scalar_type() == at::kFloat && top_lp.is_contiguous() && top_lp.numel() == rows * n &&
+                  top_ids.is_contiguous() && top_ids.numel() == rows * n, "logprobs_merge: outputs");
+  c10::DeviceGuard g(records.device());
+  bfly::launch_logprobs_merge(records.data_ptr<float>(), tp, rows, n, chosen_lp.data_ptr<float>(),
+                              top_ids.data_ptr<int>(), top_lp.data_ptr<float>(), cur_stream());
+}
+
 // Exact top-k / top-p radix select (sample.hip). `ws` is one zeroed f32 buffer holding
 // state [rows, 8] | smax [rows] (int32 bits) | hist [rows, 512].
 struct TkpViews { float* state; int* smax; float* hist; };
@@ -1257,6 +1299,10 @@ TORCH_LIBRARY(bfly, m) {
   m.def("sample_merge(Tensor allp, Tensor(a!) out) -> ()");
   m.def("sample(Tensor logits, Tensor? temps, Tensor? seeds, int vstart, Tensor(a!) out_ids, "
         "Tensor(b!) out_scores, Tensor(c!) workspace, Tensor? thresh=None, bool check_finite=False) -> ()");
+  m.def("logprobs_workspace_size(int rows, int V, int n) -> int", &logprobs_workspace_size);
+  m.def("logprobs_partial(Tensor logits, Tensor ids, int n, int vstart, Tensor(a!) record, "
+        "Tensor(b!) workspace) -> ()");
+  m.def("logprobs_merge(Tensor records, Tensor(a!) chosen_lp, Tensor(b!) top_ids, Tensor(c!) top_lp) -> ()");
   m.def("tkp_begin(Tensor logits, Tensor temps, Tensor top_k, Tensor top_p, Tensor(a!) ws) -> ()");
   m.def("tkp_pass(Tensor logits, Tensor temps, Tensor(a!) ws, int pass_, int phase) -> ()");
   m.def("tkp_select(Tensor top_p, Tensor(a!) ws, int rows, int pass_, int phase) -> ()");
@@ -1351,6 +1397,8 @@ TORCH_LIBRARY_IMPL(bfly, CUDA, m) {
   m.impl("sample_merge", &sample_merge);
   m.impl("init_hash", &init_hash);
   m.impl("sample", &sample);
+  m.impl("logprobs_partial", &logprobs_partial);
+  m.impl("logprobs_merge", &logprobs_merge);
   m.impl("tkp_begin", &tkp_begin);
   m.impl("tkp_pass", &tkp_pass);
   m.impl("tkp_select", &tkp_select);

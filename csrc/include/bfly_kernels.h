@@ -103,6 +103,24 @@ void launch_tkp_select(const float* top_p, float* state, float* hist, int rows, 
                        hipStream_t stream);
 void launch_tkp_final(const float* state, int rows, float* thresh, hipStream_t stream);
 
+// logprobs.hip: log-softmax statistics and the n most likely tokens of each row of a (vocab
+// shard of) logits. partial: record [rows][3 + 2n] f32 = (max, sum exp(x - max), logit of
+// ids[row] or -inf when it lies outside the shard, n x (logit, global id; -inf, -1 = none)).
+// merge: records [tp][rows][3 + 2n] -> chosen_lp [rows], top_ids / top_lp [rows][n].
+constexpr int kLogprobsMaxN = 20;
+constexpr int kLogprobsChunk = 4096;
+constexpr int kLogprobsMaxChunks = 64;
+inline int logprobs_chunks(int V) { return (V + kLogprobsChunk - 1) / kLogprobsChunk; }
+// workspace of launch_logprobs_partial in u64 words
+inline size_t logprobs_workspace_words(long rows, int V, int n) {
+  return (size_t)rows * logprobs_chunks(V) * (2 + n);
+}
+void launch_logprobs_partial(const bf16* logits, long row_stride, int rows, int V, int vstart,
+                             const int* ids, int n, uint64_t* workspace, float* record,
+                             hipStream_t stream);
+void launch_logprobs_merge(const float* records, int tp, int rows, int n, float* chosen_lp,
+                           int* top_ids, float* top_lp, hipStream_t stream);
+
 // gemm.hip
 GemmPlan plan_gemm(int M, int N, int K);
 size_t gemm_workspace_bytes(int M, int N, int K);
