@@ -687,11 +687,14 @@ def linear_silu_gate(x, w, gates, e0: int, num_local: int, packed=None):
     return out
 
 
+# plan kind names by number; "mixed": tile plan with column tiles of two widths (bn wide, wk narrow)
+GEMM_KINDS = ("skinny", "tile", "big", "dec", "big8", "mid8", "big4", "mid4", "mixed")
+
+
 def gemm_plan(M: int, N: int, K: int) -> dict:
     load_library()
     k, mt, nt, bm, bn, sk, wk = torch.ops.bfly.gemm_plan(M, N, K)
-    return {"kind": ("skinny", "tile", "big", "dec", "big8", "mid8", "big4", "mid4")[k], "mt": mt, "nt": nt, "wk": wk, "bm": bm, "bn": bn,
-            "splitk": sk}
+    return {"kind": GEMM_KINDS[k], "mt": mt, "nt": nt, "wk": wk, "bm": bm, "bn": bn, "splitk": sk}
 
 
 def attn_prefill(q, k, v, cu_seqlens, max_seqlen: int, scale: float, causal: bool = True,

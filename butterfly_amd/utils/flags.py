@@ -57,6 +57,9 @@ define("BFLY_CUSTOM_AR_2SHOT_BYTES", 512 << 10, int, "IPC all-reduces of at leas
        "ranks run as reduce-scatter + all-gather (2S/W bytes per link instead of S; 0 = always one-shot)")
 define("BFLY_GEMM_TUNED", True, _bool, "consult the measured GEMM plan table (0: heuristic plans only; read by the kernel library)")
 define("BFLY_GEMM_NT_WEIGHTS", True, _bool, "stream decode GEMM weights with the non-temporal policy (read by the kernel library)")
+define("BFLY_GEMM_MIXED_TILES", 1, int, "decode GEMM column tiles of two widths (128 + 96) in one launch, so every CU "
+       "carries the same columns: 0 = never, 1 = the measured shapes on their packed weight (gemm.hip kPackedTuned), "
+       "2 = every decode tile plan whose N splits (read by the kernel library)")
 define("BFLY_GEMM_PLAN", "", str, "force GEMM plans for whole-model A/B runs: \"N,K,Mbucket:kind,mt,nt,wk,bm,bn,sk;...\" "
        "(read by the kernel library)")
 define("BFLY_ATTN_XCD", 1, int, "prefill attention: XCD-aware item walk (0: plain order; read by the kernel library)")

@@ -577,15 +577,25 @@ int64_t gemm_packed_check(int64_t M, int64_t N, int64_t K, int64_t epilogue) {
                                   nullptr, true);
 }
 
-// Benchmark / tuning entry: run an explicit plan [kind, mt, nt, wk, bm, bn, sk].
+// Dry run of an explicit plan [kind, mt, nt, wk, bm, bn, sk]: 0 when it can run the shape.
+int64_t gemm_plan_check(std::vector<int64_t> plan, int64_t M, int64_t N, int64_t K, int64_t epilogue, bool packed) {
+  TORCH_CHECK(plan.size() == 7, "gemm_plan_check: plan");
+  bfly::GemmPlan p{};
+  p.kind = plan[0]; p.mt = plan[1]; p.nt = plan[2]; p.wk = plan[3]; p.bm = plan[4]; p.bn = plan[5]; p.sk = plan[6];
+  return bfly::gemm_plan_check(p, (int)M, (int)N, (int)K, (int)epilogue, packed);
+}
+
+// Benchmark / tuning entry: run an explicit plan [kind, mt, nt, wk, bm, bn, sk]. `packed`: `w` is
+// the weight's pack_w256 copy (plans with a packed form only).
 void gemm_with_plan(const Tensor& x, const Tensor& w, Tensor& out, std::vector<int64_t> plan,
                     int64_t epilogue, const c10::optional<Tensor>& workspace,
-                    const c10::optional<Tensor>& bias) {
+                    const c10::optional<Tensor>& bias, bool packed) {
   CHECK_GPU(x); CHECK_BF16(x); CHECK_BF16(w); CHECK_BF16(out);
   TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && out.dim() == 2 && plan.size() == 7, "gemm_with_plan: args");
   CHECK_INNER(x); CHECK_INNER(w); CHECK_INNER(out);
   const int M = x.size(0), K = x.size(1), N = w.size(0);
   TORCH_CHECK(w.size(1) == K, "gemm_with_plan: K mismatch");
+  TORCH_CHECK(!packed || (w.is_contiguous() && N % 256 == 0 && K % 64 == 0), "gemm_with_plan: packed weight");
   const int nout = epilogue == bfly::EPI_SILU ? N / 2 : N;
   TORCH_CHECK(out.size(0) == M && out.size(1) == nout, "gemm_with_plan: out shape");
   bfly::GemmPlan p{};
@@ -605,7 +615,7 @@ void gemm_with_plan(const Tensor& x, const Tensor& w, Tensor& out, std::vector<i
   TORCH_CHECK(epilogue != bfly::EPI_BIAS || bp != nullptr, "gemm_with_plan: bias epilogue needs a bias");
   c10::DeviceGuard g(x.device());
   const int rc = bfly::launch_gemm_plan(p, bf(x), x.stride(0), bf(w), w.stride(0), M, N, K, epilogue,
-                                        bp, bf(out), out.stride(0), ws, ws_bytes, cur_stream());
+                                        bp, bf(out), out.stride(0), ws, ws_bytes, cur_stream(), packed);
   TORCH_CHECK(rc == 0, "gemm_with_plan: plan rejected (rc=", rc, ")");
 }
 
@@ -1324,7 +1334,10 @@ TORCH_LIBRARY(bfly, m) {
   m.def("gemm_w8_workspace_size(int M, int N, int K) -> int",
         [](int64_t M, int64_t N, int64_t K) -> int64_t { return (int64_t)bfly::gemm_w8_workspace_bytes(M, N, K); });
   m.def("gemm_with_plan(Tensor x, Tensor w, Tensor(a!) out, int[] plan, int epilogue, Tensor(b!)? workspace, "
-        "Tensor? bias=None) -> ()");
+        "Tensor? bias=None, bool packed=False) -> ()");
+  m.def("gemm_plan_check(int[] plan, int M, int N, int K, int epilogue, bool packed=False) -> int", &gemm_plan_check);
+  m.def("gemm_mixed_tiles_mode(int mode) -> int",
+        [](int64_t mode) -> int64_t { return bfly::gemm_mixed_tiles_mode((int)mode); });
   m.def("gemm_workspace_size(int M, int N, int K) -> int", &gemm_workspace_size);
   m.def("gemm_plan(int M, int N, int K) -> int[]", &gemm_plan);
   m.def("gemm_check(int M, int N, int K, int epilogue) -> int",

@@ -29,7 +29,8 @@ struct RowScale {
 
 struct GemmPlan {
   int kind;  // 0 = skinny (decode), 1 = LDS-tiled, 3 = decode ring, 5 = mid-M 8-wave,
-             // 4 = 256x256 8-phase big tile (BK 64, prefill; kind 2 was the removed ring kernel)
+             // 4 = 256x256 8-phase big tile (BK 64, prefill; kind 2 was the removed ring kernel),
+             // 8 = LDS-tiled with column tiles of two widths (bn wide, wk narrow) in one launch
   int mt, nt;
   int wk;    // skinny: waves splitting K inside a workgroup (1, 2, 4)
   int bm, bn;
@@ -126,7 +127,13 @@ GemmPlan plan_gemm(int M, int N, int K);
 size_t gemm_workspace_bytes(int M, int N, int K);
 int launch_gemm_plan(const GemmPlan& p, const bf16* X, long ldx, const bf16* W, long ldw, int M,
                      int N, int K, int epi, const bf16* bias, bf16* out, long ldo, float* ws,
-                     size_t ws_bytes, hipStream_t stream);
+                     size_t ws_bytes, hipStream_t stream, bool packed = false);
+// 0 when `p` can run this shape and epilogue (`packed`: over a pack_w256 weight), < 0 otherwise;
+// launches nothing
+int gemm_plan_check(const GemmPlan& p, int M, int N, int K, int epi, bool packed);
+// Mixed-width tile plans: 0 = never, 1 = the measured shapes, 2 = every shape they fit. Sets the
+// mode (a value outside 0..2 only reads it) and returns the previous one.
+int gemm_mixed_tiles_mode(int mode);
 int gemm_check(int M, int N, int K, int epi);
 // 0 if the auto plan for this shape takes a RowScale (tile and decode-ring kernels)
 int gemm_rowscale_check(int M, int N, int K, int epi);

@@ -292,7 +292,14 @@ __device__ __forceinline__ bf16x8 lds_frag(const char* lds, int row, int chunk) 
 // `pslab`: this workgroup's split-K slab from row m0 on (nullptr: apply the epilogue).
 // `rsc`: RMSNorm row scale of a consumer GEMM (RowScale, ss == nullptr: none), applied to the
 // accumulators first, so split-K slabs, the bias and the SiLU all see the normalised rows.
-template <int TI, int TJ>
+// SFORM (the mixed-width kernel): the row-scaled SwiGLU h = silu(g s) (u s) in a fixed operation
+// order. The build's fast-math reassociates that product, and not alike in every instantiation:
+// the uniform 32- and 64-row tile kernels come out as ((s s) g) u / (1 + exp2(g (-log2e s))), the
+// 16-row one as (s s) (g u) / ..., and a tile body of another width would pick its own. The
+// mixed kernel must be bitwise its uniform twin, so it spells that order out (1: the 32 / 64-row
+// order, 2: the 16-row one; 0: left to the compiler, every other kernel). Without a row scale
+// s = 1 and every order gives the same bits.
+template <int TI, int TJ, int SFORM = 0>
 __device__ __forceinline__ void tile_epilogue(const f32x4 (&acc)[TI][TJ], int mw, int nw, int lane,
                                               int M, int N, int epi, const bf16* __restrict__ bias,
                                               bf16* __restrict__ out, long ldo, float* __restrict__ pslab,
@@ -341,8 +348,19 @@ __device__ __forceinline__ void tile_epilogue(const f32x4 (&acc)[TI][TJ], int mw
         if constexpr (TJ % 2 == 0) {   // gate/up 16-row groups pair up inside the wave
           if (j & 1) continue;
           f32x4 h;
+          if constexpr (SFORM != 0) {
+#pragma clang fp reassociate(off) contract(off)
+            const float s = sc[i], s2 = s * s, c = -1.44269504f * s;
 #pragma unroll
-          for (int r = 0; r < 4; ++r) h[r] = silu(acc[i][j][r] * sc[i]) * (acc[i][j + 1][r] * sc[i]);
+            for (int r = 0; r < 4; ++r) {
+              const float g = acc[i][j][r], u = acc[i][j + 1][r];
+              const float rcp = __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(g * c) + 1.f);
+              h[r] = (SFORM == 1 ? (s2 * g) * u : s2 * (g * u)) * rcp;
+            }
+          } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) h[r] = silu(acc[i][j][r] * sc[i]) * (acc[i][j + 1][r] * sc[i]);
+          }
           const int f = nw / 2 + 16 * (j / 2) + lc;
           if (epi == EPI_SILU_GATE) {   // the 4 columns share an expert (gF % 16 == 0)
             const float g = rsc.gate[(long)m * rsc.gld + rsc.ge0 + f / rsc.gF];
@@ -467,6 +485,121 @@ gemm_tile_kernel(const bf16* __restrict__ X, long ldx, const bf16* __restrict__ 
   }
   tile_epilogue<TI, TJ>(acc, m0 + wm * WM, n0 + wn * WN, lane, M, N, epi, bias, out, ldo,
                         part ? part + (long)ksplit * m_slab * N + (long)m0 * N : nullptr, m0, rsc);
+}
+
+// gemm_tile_kernel's pipeline and epilogue for one output tile [m0, m0 + BM) x [n0, n0 + BN) of a
+// launch whose workgroups differ in BN (gemm_tile_mixed_kernel). The waves form a WMW x (4 / WMW)
+// grid; a BN that the waves along N cannot split into multiples of 16 columns (96 over four
+// waves) gives each wave 32 columns and leaves the surplus wave to stage and synchronise only.
+// SFORM: the SwiGLU operation order of the uniform kernel with BM rows (tile_epilogue).
+template <int BM, int BN, int WMW, int STAGES, bool PACKW, int SFORM>
+__device__ __forceinline__ void tile_body(const bf16* __restrict__ X, long ldx, const bf16* __restrict__ W,
+                                          long ldw, int M, int N, int K, int epi,
+                                          const bf16* __restrict__ bias, bf16* __restrict__ out, long ldo,
+                                          float* __restrict__ part, int m0, int n0, const RowScale& rsc,
+                                          char* smem) {
+  constexpr int WNW = 4 / WMW;                // waves along M x waves along N
+  constexpr int WM = BM / WMW;
+  constexpr int WN = BN % (16 * WNW) == 0 ? BN / WNW : 32;  // per-wave output tile
+  constexpr int NACT = BN / WN;               // waves along N that own columns
+  static_assert(BN % WN == 0 && NACT <= WNW && WM % 16 == 0 && WN % 16 == 0, "wave layout");
+  constexpr int TI = WM / 16, TJ = WN / 16;  // MFMA tiles per wave
+  constexpr int A_BYTES = BM * kBK * 2, B_BYTES = BN * kBK * 2;
+  constexpr int LPW = stage_loads<BM>() + stage_loads<BN>();  // glds per wave per stage
+  constexpr int STAGE_BYTES = A_BYTES + B_BYTES;  // one buffer = [A tile | B tile]
+
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int wm = wid / WNW, wn = wid % WNW;
+  const bool active = NACT == WNW || wn < NACT;
+  const int ksplit = (int)blockIdx.y;
+  const int nsplit = (int)gridDim.y;
+
+  const int ktiles = K / kBK;
+  const int kt0 = (int)(((long)ktiles * ksplit) / nsplit);
+  const int kt1 = (int)(((long)ktiles * (ksplit + 1)) / nsplit);
+  // each W byte read by one workgroup: stream it non-temporally
+  const bool w_nt = M <= BM && g_tile_w_nt;
+
+  f32x4 acc[TI][TJ];
+#pragma unroll
+  for (int i = 0; i < TI; ++i)
+#pragma unroll
+    for (int j = 0; j < TJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+#pragma unroll
+  for (int s = 0; s < STAGES - 1; ++s) {
+    if (kt0 + s < kt1) {
+      char* b = smem + s * STAGE_BYTES;
+      tile_stage<BM>(X, ldx, m0, M, (kt0 + s) * kBK, b, wid, lane);
+      tile_stage<BN, false, PACKW>(W, ldw, n0, N, (kt0 + s) * kBK, b + A_BYTES, wid, lane, nullptr, w_nt);
+    }
+  }
+  int buf = 0;
+  for (int kt = kt0; kt < kt1; ++kt) {
+    // tiles issued after kt: min(STAGES - 2, kt1 - 1 - kt); wait until only those are pending
+    const int after = min(STAGES - 2, kt1 - 1 - kt);
+    if (STAGES >= 4 && after >= 2) vm_wait<(STAGES >= 4 ? 2 : 0) * LPW>();
+    else if (STAGES >= 3 && after >= 1) vm_wait<LPW>();
+    else vm_wait<0>();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    if (kt + STAGES - 1 < kt1) {
+      int nbuf = buf + STAGES - 1;
+      if (nbuf >= STAGES) nbuf -= STAGES;
+      char* nb = smem + nbuf * STAGE_BYTES;
+      tile_stage<BM>(X, ldx, m0, M, (kt + STAGES - 1) * kBK, nb, wid, lane);
+      tile_stage<BN, false, PACKW>(W, ldw, n0, N, (kt + STAGES - 1) * kBK, nb + A_BYTES, wid, lane, nullptr, w_nt);
+    }
+    const char* As = smem + buf * STAGE_BYTES;
+    const char* Bs = As + A_BYTES;
+    if (active) {
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        bf16x8 af[TI], bfr[TJ];
+#pragma unroll
+        for (int i = 0; i < TI; ++i) af[i] = lds_frag(As, wm * WM + 16 * i + (lane & 15), ks * 4 + (lane >> 4));
+#pragma unroll
+        for (int j = 0; j < TJ; ++j) bfr[j] = lds_frag(Bs, wn * WN + 16 * j + (lane & 15), ks * 4 + (lane >> 4));
+#pragma unroll
+        for (int i = 0; i < TI; ++i)
+#pragma unroll
+          for (int j = 0; j < TJ; ++j) acc[i][j] = mfma16(bfr[j], af[i], acc[i][j]);   // C^T tile
+      }
+    }
+    if (++buf == STAGES) buf = 0;
+  }
+  if (active)
+    tile_epilogue<TI, TJ, SFORM>(acc, m0 + wm * WM, n0 + wn * WN, lane, M, N, epi, bias, out, ldo,
+                                 part ? part + (long)ksplit * M * N + (long)m0 * N : nullptr, m0, rsc);
+}
+
+// Two column-tile widths in one launch, for a weight stream whose uniform tile count leaves
+// the CUs unevenly loaded (Llama-3-70B gate/up, N = 57344: 448 tiles of 128 columns put 256
+// columns on 192 CUs and 128 on the rest; 256 tiles of 128 plus 256 of 96 put 224 on every CU).
+// `nwide` tiles of BNW columns cover [0, nwide * BNW), the tiles of BNN columns the rest. The
+// wide tiles come first in launch order: the dispatcher hands every CU one workgroup before it
+// doubles up, so with two workgroups per CU each CU ends with one of each width. Each width has
+// its own bijective XCD remap. An output element's K order does not depend on the width or the
+// wave layout, and the epilogue keeps the uniform kernel's operation order (SFORM), so the result
+// is bitwise that of the uniform tile plan.
+template <int BM, int BNW, int WMWW, int BNN, int WMWN, int STAGES, bool PACKW>
+__global__ void __launch_bounds__(kTileThreads)
+gemm_tile_mixed_kernel(const bf16* __restrict__ X, long ldx, const bf16* __restrict__ W, long ldw,
+                       int M, int N, int K, int epi, const bf16* __restrict__ bias,
+                       bf16* __restrict__ out, long ldo, float* __restrict__ part, int nwide, RowScale rsc) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int SFORM = BM == 16 ? 2 : 1;   // the uniform BM-row kernel's SwiGLU order
+  const int mtiles = (M + BM - 1) / BM;
+  const int wide_wgs = nwide * mtiles, b = (int)blockIdx.x;
+  if (b < wide_wgs) {
+    const int tile = xcd_remap(b, wide_wgs);
+    tile_body<BM, BNW, WMWW, STAGES, PACKW, SFORM>(X, ldx, W, ldw, M, N, K, epi, bias, out, ldo, part,
+                                                   (tile % mtiles) * BM, (tile / mtiles) * BNW, rsc, smem);
+  } else {
+    const int tile = xcd_remap(b - wide_wgs, (int)gridDim.x - wide_wgs);
+    tile_body<BM, BNN, WMWN, STAGES, PACKW, SFORM>(X, ldx, W, ldw, M, N, K, epi, bias, out, ldo, part,
+                                                   (tile % mtiles) * BM, nwide * BNW + (tile / mtiles) * BNN, rsc, smem);
+  }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1485,6 +1618,28 @@ static void run_tile(const bf16* X, long ldx, const bf16* W, long ldw, int M, in
       nullptr, nullptr, nullptr, 0, rsc);
 }
 
+// `nwide` column tiles of BNW then `nnarrow` of BNN (gemm_tile_mixed_kernel); the dynamic LDS is
+// per launch, so it is sized for the wide tile.
+template <int BM, int BNW, int WMWW, int BNN, int WMWN, int STAGES, bool PACKW>
+static void run_tile_mixed(const bf16* X, long ldx, const bf16* W, long ldw, int M, int N, int K,
+                           int epi, const bf16* bias, bf16* out, long ldo, float* ws, int sk,
+                           hipStream_t stream, const RowScale& rsc, int nwide, int nnarrow) {
+  init_nt_policy();
+  const int mtiles = (M + BM - 1) / BM;
+  const size_t lds = (size_t)STAGES * (BM + BNW) * kBK * 2;
+  const dim3 grid((nwide + nnarrow) * mtiles, sk);
+  static bool attr_set = false;
+  if (!attr_set && lds > 65536) {
+    hipFuncSetAttribute(
+        reinterpret_cast<const void*>(&gemm_tile_mixed_kernel<BM, BNW, WMWW, BNN, WMWN, STAGES, PACKW>),
+        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    attr_set = true;
+  }
+  gemm_tile_mixed_kernel<BM, BNW, WMWW, BNN, WMWN, STAGES, PACKW><<<grid, kTileThreads, lds, stream>>>(
+      X, ldx, W, PACKW ? (long)K : ldw, M, N, K, epi, bias, out, ldo, sk > 1 ? splitk_part(ws) : nullptr, nwide,
+      rsc);
+}
+
 template <int BM, int BN, int NWM, int NWN, int SW>
 static void run_dec(const bf16* X, long ldx, const bf16* W, long ldw, int M, int N, int K,
                     int epi, const bf16* bias, bf16* out, long ldo, float* ws, int sk,
@@ -1613,28 +1768,49 @@ static const std::vector<PlanOverride>& plan_overrides() {
   return v;
 }
 
-GemmPlan plan_gemm(int M, int N, int K) {
-  if (!plan_overrides().empty()) {
-    static const int kB[] = {1, 16, 32, 64, 128, 256, 512};
-    int bucket = 0;
-    for (int b : kB)
-      if (b >= M) { bucket = b; break; }
-    for (const PlanOverride& o : plan_overrides())
-      if (o.N == N && o.K == K && o.M == bucket) return o.p;
+// Mixed-width tile plans {8, stages, 0, narrow width, BM, wide width, sk} (gemm_tile_mixed_kernel):
+// equal counts of wide and narrow column tiles, so N must be a multiple of the two widths' sum.
+// BFLY_GEMM_MIXED_TILES / gemm_mixed_tiles_mode: 0 = never, 1 = the measured shapes, on the
+// packed weight only (kPackedTuned: on the row-major weight the mixed grid measured slower, 176
+// against 160 us for the Llama-3-70B gate/up), 2 = every decode tile plan of 128 columns whose N
+// splits, on either weight (tests, A/B runs).
+constexpr int kMixedWide = 128, kMixedNarrow = 96;
+static int g_mixed_mode = -1;
+
+int gemm_mixed_tiles_mode(int mode) {
+  if (g_mixed_mode < 0) {
+    const char* e = getenv("BFLY_GEMM_MIXED_TILES");
+    g_mixed_mode = e && e[0] >= '0' && e[0] <= '2' ? e[0] - '0' : 1;
   }
-  if (!tuned_enabled()) return plan_gemm_heuristic(M, N, K);
-  // token-count buckets of the sweep: M uses the entry of its bucket, or the heuristic plan
-  // when the sweep found nothing better there
+  const int prev = g_mixed_mode;
+  if (mode >= 0 && mode <= 2) g_mixed_mode = mode;
+  return prev;
+}
+
+// Mode 2: the mixed twin of a decode tile plan of 128 columns, where N splits.
+static GemmPlan mixed_plan(const GemmPlan& p, int N) {
+  if (gemm_mixed_tiles_mode(-1) != 2 || p.kind != 1 || p.nt != 0 || p.bn != kMixedWide || p.bm > 64 || p.mt != 3 ||
+      N % (kMixedWide + kMixedNarrow) != 0)
+    return p;
+  return GemmPlan{8, 3, 0, kMixedNarrow, p.bm, kMixedWide, p.sk};
+}
+
+GemmPlan plan_gemm(int M, int N, int K) {
   static const int kBuckets[] = {1, 16, 32, 64, 128, 256, 512};
   int bucket = 0;
   for (int b : kBuckets)
     if (b >= M) { bucket = b; break; }
+  for (const PlanOverride& o : plan_overrides())
+    if (o.N == N && o.K == K && o.M == bucket) return o.p;
+  if (!tuned_enabled()) return mixed_plan(plan_gemm_heuristic(M, N, K), N);
+  // token-count buckets of the sweep: M uses the entry of its bucket, or the heuristic plan
+  // when the sweep found nothing better there
   if (bucket == 0) return plan_gemm_heuristic(M, N, K);
   for (const TunedPlan& t : kTuned)
     if (t.N == N && t.K == K && t.M == bucket)   // 256x256 entries (swept on big8) run big4:
       return t.kind == 4 ? GemmPlan{6, 0, 0, 0, 256, 256, t.sk}   // >= big8 at every swept M / sk
                          : GemmPlan{t.kind, t.mt, t.nt, t.wk, t.bm, t.bn, t.sk};
-  return plan_gemm_heuristic(M, N, K);
+  return mixed_plan(plan_gemm_heuristic(M, N, K), N);
 }
 
 static GemmPlan plan_gemm_heuristic(int M, int N, int K) {
@@ -1702,10 +1878,12 @@ static int run_plan(const GemmPlan& p, const bf16* X, long ldx, const bf16* W, l
                     hipStream_t stream, bool dry = false, bool defer = false,
                     const RowScale* rs = nullptr, bool packed = false) {
   const RowScale rsc = rs ? *rs : RowScale{nullptr, 0, 0.f, 0.f};
-  if (rs != nullptr && p.kind != 1 && p.kind != 3 && p.kind != 5 && p.kind != 7) return -4;   // row scale: tile / ring / mid epilogues
-  if (epi == EPI_SILU_GATE && (p.kind != 1 || p.sk != 1)) return -4;   // gate: tile epilogue, no slabs
-  // packed (pack_w256) weights: the tile plans mark it with nt = 1, the mid-M kernels take it here
-  if (packed && p.kind != 5 && p.kind != 7) return -5;
+  if (rs != nullptr && p.kind != 1 && p.kind != 3 && p.kind != 5 && p.kind != 7 && p.kind != 8) return -4;   // row scale: tile / ring / mid epilogues
+  if (epi == EPI_SILU_GATE && ((p.kind != 1 && p.kind != 8) || p.sk != 1)) return -4;   // gate: tile epilogue, no slabs
+  // packed (pack_w256) weights: `packed` alone picks the kernel that reads them (a plan's `nt`
+  // is no layout marker: the row-major entries run a tile plan that carries nt = 1 on the
+  // row-major kernel); the tile, mixed-tile and mid-M kernels have a packed form
+  if (packed && p.kind != 1 && p.kind != 5 && p.kind != 7 && p.kind != 8) return -5;
   if (p.kind == 4) {
     // 8-phase big tile: every split needs >= 2 K-tiles of 64
     if (N % 256 != 0 || K % 64 != 0 || K / 64 < 2 * p.sk) return -1;
@@ -1783,7 +1961,34 @@ static int run_plan(const GemmPlan& p, const bf16* X, long ldx, const bf16* W, l
 #undef SK_WK
 #undef SK_CASE
     if (!done) return -2;
-  } else if (p.kind == 1 && p.nt == 1) {
+  } else if (p.kind == 8) {
+    // mixed-width tiles: {8, stages, 0, narrow width, BM, wide width, sk}; equal counts of the two
+    // widths (every CU's pair of workgroups then holds the same columns), so a shape whose N is
+    // no multiple of their sum has no solution and is refused
+    if (p.bn != kMixedWide || p.wk != kMixedNarrow || N % (p.bn + p.wk) != 0 || K % kBK != 0 || K / kBK < p.sk ||
+        p.sk < 1 || (packed && N % 256 != 0))
+      return -1;
+    if ((epi == EPI_SILU || epi == EPI_SILU_GATE) && (p.bn % 32 != 0 || p.wk % 32 != 0)) return -1;
+    const int npair = N / (p.bn + p.wk);
+    if (p.sk > 1 && 2L * npair * ((M + p.bm - 1) / p.bm) > kSplitCounters) return -1;
+    bool done = false;
+    const int st = p.mt > 0 ? p.mt : 3;
+#define MX_CASE(BM_, WMWW_, WMWN_)                                                                    \
+  if (!done && p.bm == BM_ && st == 3) {                                                              \
+    if (!dry && packed)                                                                               \
+      run_tile_mixed<BM_, kMixedWide, WMWW_, kMixedNarrow, WMWN_, 3, true>(X, ldx, W, ldw, M, N, K, epi, bias, out, \
+                                                                           ldo, ws, p.sk, stream, rsc, npair, npair); \
+    else if (!dry)                                                                                    \
+      run_tile_mixed<BM_, kMixedWide, WMWW_, kMixedNarrow, WMWN_, 3, false>(X, ldx, W, ldw, M, N, K, epi, bias, out, \
+                                                                            ldo, ws, p.sk, stream, rsc, npair, npair); \
+    done = true;                                                                                      \
+  }
+    // 64 rows: 2 x 2 waves on the wide tile, 4 x 1 on the narrow one (6 MFMA columns per wave);
+    // 16 / 32 rows: 1 x 4 waves, three of them own 32 columns of the narrow tile
+    MX_CASE(16, 1, 1) MX_CASE(32, 1, 1) MX_CASE(64, 2, 4)
+#undef MX_CASE
+    if (!done) return -2;
+  } else if (p.kind == 1 && packed) {
     // tile plan over a K-tile-blocked weight (pack_w256 layout): 16 / 32 / 64-row tiles of 128 /
     // 256 columns (the packed layout only changes the weight stage's addresses, so every decode
     // tile the row-major table picks, down to the B = 1 bucket, has its packed twin)
@@ -1838,11 +2043,17 @@ static int run_plan(const GemmPlan& p, const bf16* X, long ldx, const bf16* W, l
 
 int launch_gemm_plan(const GemmPlan& p, const bf16* X, long ldx, const bf16* W, long ldw, int M,
                      int N, int K, int epi, const bf16* bias, bf16* out, long ldo, float* ws,
-                     size_t ws_bytes, hipStream_t stream) {
+                     size_t ws_bytes, hipStream_t stream, bool packed) {
   if (M <= 0) return 0;
   if (p.sk > 1 && (ws == nullptr || ws_bytes < kCounterBytes + (size_t)p.sk * M * N * sizeof(float)))
     return -3;
-  return run_plan(p, X, ldx, W, ldw, M, N, K, epi, bias, out, ldo, ws, stream);
+  return run_plan(p, X, ldx, W, packed ? (long)K : ldw, M, N, K, epi, bias, out, ldo, ws, stream, false, false,
+                  nullptr, packed);
+}
+
+int gemm_plan_check(const GemmPlan& p, int M, int N, int K, int epi, bool packed) {
+  return run_plan(p, nullptr, 0, nullptr, 0, M, N, K, epi, nullptr, nullptr, 0, nullptr, nullptr, true, false,
+                  nullptr, packed);
 }
 
 // The plan for this call: the tuned/heuristic plan, or the heuristic one when a table entry
@@ -1980,6 +2191,11 @@ int launch_gemm(const bf16* X, long ldx, const bf16* W, long ldw, int M, int N, 
 struct PackedTuned { int N, K, M; GemmPlan p; };
 static const PackedTuned kPackedTuned[] = {
     {8192, 8192, 64, {1, 3, 1, 2, 64, 128, 4}},   // 70B O: 29.3 us vs 32.7 (row-major table plan, split-K 8)
+    // 70B gate/up on 256 tiles of 128 + 256 of 96 columns instead of 448 of 128 (every CU then carries
+    // 224 columns): 138 us vs 147 in the decode step, 28.15 -> 27.54 ms per step
+    // (profiles/balanced_tiles/README.md). Not Mixtral 8x7B's dense expert gate/up (229376 x 4096,
+    // 1792 tiles -> 1024 + 1024): its step measured slower with it, 17.70 -> 18.10 ms
+    {57344, 8192, 64, {8, 3, 0, kMixedNarrow, 64, kMixedWide, 1}},
     {4096, 4096, 1, {-1, 0, 0, 0, 0, 0, 0}},      // 8B O: row-major 13.7 us vs 14.2 packed at M = 64;
     {4096, 4096, 16, {-1, 0, 0, 0, 0, 0, 0}},     // packing O / down measured 1-2 % slower per step
     {4096, 4096, 32, {-1, 0, 0, 0, 0, 0, 0}},     // at B = 1 (kinds_b1_ab.log)
@@ -2000,6 +2216,7 @@ int launch_gemm_packed(const bf16* X, long ldx, const bf16* Wp, int M, int N, in
     for (const PackedTuned& t : kPackedTuned)
       if (t.N == N && t.K == K && t.M == bucket) {
         if (t.p.kind < 0) return -2;
+        if (t.p.kind == 8 && gemm_mixed_tiles_mode(-1) == 0) break;
         if (run_plan(t.p, nullptr, 0, nullptr, 0, M, N, K, epi, nullptr, nullptr, 0, nullptr, nullptr, true) == 0)
           p = t.p;
         break;
@@ -2015,15 +2232,15 @@ int launch_gemm_packed(const bf16* X, long ldx, const bf16* Wp, int M, int N, in
   }
   // mid-M kernels (kinds 5 / 7): their weight DMA takes the packed layout as a template flag
   const bool mid = (p.kind == 5 || p.kind == 7) && (p.bn == 128 || p.bn == 256);
-  if (!mid && (p.kind != 1 || (p.bm != 16 && p.bm != 32 && p.bm != 64) || (p.bn != 128 && p.bn != 256))) return -2;
+  const bool tile = (p.kind == 1 && (p.bn == 128 || p.bn == 256)) || p.kind == 8;
+  if (!mid && (!tile || (p.bm != 16 && p.bm != 32 && p.bm != 64))) return -2;
   if (!dry && p.sk > 1 && (ws == nullptr || ws_bytes < kCounterBytes + (size_t)p.sk * M * N * sizeof(float)))
     return -3;
-  if (!mid) p.nt = 1;
   if (dry)
     return run_plan(p, nullptr, 0, nullptr, 0, M, N, K, epi, nullptr, nullptr, 0, nullptr, nullptr, true, false,
-                    nullptr, mid);
+                    nullptr, true);
   const bool d = defer && p.sk > 1;
-  const int rc = run_plan(p, X, ldx, Wp, K, M, N, K, epi, nullptr, out, ldo, ws, stream, false, d, rs, mid);
+  const int rc = run_plan(p, X, ldx, Wp, K, M, N, K, epi, nullptr, out, ldo, ws, stream, false, d, rs, true);
   if (rc != 0) return rc;
   return d ? p.sk : 1;     // split count of slabs left in the workspace (deferred), else 1
 }

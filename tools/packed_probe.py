@@ -42,6 +42,8 @@ def table_plan(M, N, K):
     return [kinds.index(p["kind"]), p["mt"], p["nt"], p["wk"], p["bm"], p["bn"], p["splitk"]]
 
 
+# Plans with nt = 1 label the packed cases of this tool; gemm_with_plan's `packed` argument (not the
+# plan) makes the kernel read the pack_w256 layout.
 def split_k_shapes(M):
     """The table plans of the other decode projections, row-major vs packed (split-K plans,
     their reduce launch included)."""
@@ -60,7 +62,7 @@ def split_k_shapes(M):
         pk[2] = 1
         for rep in range(2):
             for case, W, p in (("rowmajor", Ws, pl), ("packed", Ps, pk)):
-                us = timeit(lambda i: torch.ops.bfly.gemm_with_plan(x, W[i % copies], out, p, 0, ws))
+                us = timeit(lambda i: torch.ops.bfly.gemm_with_plan(x, W[i % copies], out, p, 0, ws, None, p[2] == 1))
                 print(json.dumps({"rep": rep, "shape": name, "case": case, "plan": p, "us": round(us, 2),
                                   "TBps": round(N * K * 2 / us / 1e6, 3)}), flush=True)
         del Ws, Ps
@@ -99,7 +101,7 @@ def sweep(M, names):
         for rep in range(2):
             for tag, W, pl in cands:
                 try:
-                    us = timeit(lambda i: torch.ops.bfly.gemm_with_plan(x, W[i % copies], out, pl, epi, ws), iters=20)
+                    us = timeit(lambda i: torch.ops.bfly.gemm_with_plan(x, W[i % copies], out, pl, epi, ws, None, pl[2] == 1), iters=20)
                 except RuntimeError:
                     continue
                 res.setdefault(tag, []).append(us)
@@ -134,14 +136,14 @@ def main():
     ref = torch.empty_like(out)
     silu = ops.EPILOGUES["silu"]
     torch.ops.bfly.gemm_with_plan(x, Ws[0], ref, [1, 3, 0, 2, 64, 128, 1], silu, None)
-    torch.ops.bfly.gemm_with_plan(x, Ps[0], out, [1, 3, 1, 2, 64, 128, 1], silu, None)
+    torch.ops.bfly.gemm_with_plan(x, Ps[0], out, [1, 3, 1, 2, 64, 128, 1], silu, None, None, True)
     torch.cuda.synchronize()
     print(json.dumps({"bitwise_equal": bool(torch.equal(out, ref))}), flush=True)
     cases = [("rowmajor_wk2", Ws, [1, 3, 0, 2, 64, 128, 1]), ("packed_wk2", Ps, [1, 3, 1, 2, 64, 128, 1]),
              ("rowmajor_wk1", Ws, [1, 3, 0, 1, 64, 128, 1]), ("packed_wk1", Ps, [1, 3, 1, 1, 64, 128, 1])]
     for rep in range(3):
         for name, W, pl in cases:
-            us = timeit(lambda i: torch.ops.bfly.gemm_with_plan(x, W[i % copies], out, pl, silu, None))
+            us = timeit(lambda i: torch.ops.bfly.gemm_with_plan(x, W[i % copies], out, pl, silu, None, None, pl[2] == 1))
             print(json.dumps({"rep": rep, "case": name, "M": M, "N": N, "K": K, "us": round(us, 2),
                               "TBps": round(N * K * 2 / us / 1e6, 3)}), flush=True)
 
