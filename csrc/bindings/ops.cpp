@@ -482,7 +482,7 @@ int64_t gemm_packed(const Tensor& x, const Tensor& wp, Tensor& out, int64_t epil
   }
   c10::DeviceGuard g(x.device());
   return bfly::launch_gemm_packed(bf(x), x.stride(0), bf(wp), M, N, K, (int)epilogue, bf(out), out.stride(0),
-                                  cur_stream(), any ? &rs : nullptr, false, ws, ws_bytes, defer);
+                                  cur_stream(), any ? &rs : nullptr, ws, ws_bytes, defer);
 }
 
 // FP8 e4m3 weight-only linear layers (gemm_w8.hip). Codes are torch.float8_e4m3fn or uint8.
@@ -571,10 +571,9 @@ void gemm_w8(const Tensor& x, const Tensor& code, const Tensor& scale, Tensor& o
               " (rc=", rc, ")");
 }
 
-// 0 when the plan for (M, N, K, epilogue) has a packed-weight form (launch_gemm_packed dry run)
+// 0 when the plan for (M, N, K, epilogue) has a packed-weight form
 int64_t gemm_packed_check(int64_t M, int64_t N, int64_t K, int64_t epilogue) {
-  return bfly::launch_gemm_packed(nullptr, 0, nullptr, (int)M, (int)N, (int)K, (int)epilogue, nullptr, 0, nullptr,
-                                  nullptr, true);
+  return bfly::gemm_packed_check((int)M, (int)N, (int)K, (int)epilogue);
 }
 
 // Dry run of an explicit plan [kind, mt, nt, wk, bm, bn, sk]: 0 when it can run the shape.

@@ -27,14 +27,31 @@ struct RowScale {
   int gld = 0, ge0 = 0, gF = 0;
 };
 
+// GEMM plan kinds. The numbers are the wire format (torch.ops.bfly.gemm_plan / gemm_plan_check /
+// gemm_with_plan, BFLY_GEMM_PLAN, the rows of gemm_tuned.inc); 2 was the removed ring kernel.
+enum GemmKind : int { kSkinny = 0, kTile = 1, kDec = 3, kBig8 = 4, kMid8 = 5, kBig4 = 6, kMid4 = 7, kTileMixed = 8 };
+
+// A kernel family (`kind`) and the template instantiation of it; `sk` is the split-K factor of
+// every kind. What the other fields hold ("-": not read):
+//
+//   kind        kernel                  mt                    nt                      wk                 bm     bn
+//   kSkinny     gemm_skinny_kernel      16-token tiles        16-column weight tiles  waves splitting K  -      -
+//                                       (M <= 16 mt)          per wave                (1, 2, 4)
+//   kTile       gemm_tile_kernel        pipeline depth        - (1 on some table      waves along M      rows   columns
+//                                       (0: 2)                rows: no meaning)
+//   kDec        gemm_dec_kernel         weight ring depth     waves                   waves along M      rows   columns
+//   kBig8       gemm_big8_kernel        -                     -                       -                  - (256 x 256)
+//   kMid8       gemm_mid8_kernel        weight ring depth     activation ring depth   -                  rows   columns
+//                                                             (0: that of the weight)
+//   kBig4       gemm_big4_kernel        -                     -                       -                  - (256 x 256)
+//   kMid4       gemm_mid4_kernel        activation ring depth weight ring depth       -                  rows   columns
+//   kTileMixed  gemm_tile_mixed_kernel  pipeline depth        -                       narrow columns     rows   wide columns
+//                                       (0: 3)                                        (96)                      (128)
+//
+// Ring and pipeline depths count K-tiles of 64. A kind that is none of these runs as kTile.
 struct GemmPlan {
-  int kind;  // 0 = skinny (decode), 1 = LDS-tiled, 3 = decode ring, 5 = mid-M 8-wave,
-             // 4 = 256x256 8-phase big tile (BK 64, prefill; kind 2 was the removed ring kernel),
-             // 8 = LDS-tiled with column tiles of two widths (bn wide, wk narrow) in one launch
-  int mt, nt;
-  int wk;    // skinny: waves splitting K inside a workgroup (1, 2, 4)
-  int bm, bn;
-  int sk;    // split-K factor
+  int kind;   // GemmKind
+  int mt, nt, wk, bm, bn, sk;
 };
 
 // norm.hip
@@ -156,10 +173,11 @@ int launch_gemm(const bf16* X, long ldx, const bf16* W, long ldw, int M, int N, 
 // the row-major weight would run: < 0 (nothing launched) when that plan is not a 64-row tile plan.
 // `rs`: row scale and / or MoE gate (EPI_SILU_GATE). Split-K plans need `ws`; with `defer` their
 // slabs stay in it for the consumer (returns the split count), else they are reduced (returns 1).
-// `dry`: only report whether it applies (0).
 int launch_gemm_packed(const bf16* X, long ldx, const bf16* Wp, int M, int N, int K, int epi, bf16* out,
-                       long ldo, hipStream_t stream, const RowScale* rs = nullptr, bool dry = false,
-                       float* ws = nullptr, size_t ws_bytes = 0, bool defer = false);
+                       long ldo, hipStream_t stream, const RowScale* rs = nullptr, float* ws = nullptr,
+                       size_t ws_bytes = 0, bool defer = false);
+// 0 when launch_gemm_packed applies to this shape and epilogue, else its error; launches nothing
+int gemm_packed_check(int M, int N, int K, int epi);
 int launch_gemm_silu_gate(const bf16* X, long ldx, const bf16* W, long ldw, int M, int N, int K,
                           bf16* out, long ldo, const float* gates, int gld, int ge0, int gF,
                           hipStream_t stream);

@@ -29,6 +29,7 @@
 
 #include <cstdio>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "bfly_kernels.h"
 #include "bfly_kv.h"
@@ -1403,9 +1404,6 @@ gemm_mid8_kernel(const bf16* __restrict__ X, long ldx, const bf16* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------
-// Host dispatch
-// ---------------------------------------------------------------------------------------
-// ---------------------------------------------------------------------------------------
 // Mid-M one-wave-per-SIMD GEMM (plan kind 7, "mid4"): big4's structure on 128x128 / 256x128 /
 // 128x256 tiles for the TP-shard and large-batch decode projections (M = 128-512), where
 // split-K fills the chip and each workgroup walks only 8-30 K-tiles. 4 waves in 2 x 2, each
@@ -1574,21 +1572,27 @@ gemm_mid4_kernel(const bf16* __restrict__ X, long ldx, const bf16* __restrict__ 
                         part ? part + (long)blockIdx.y * M * N + (long)m0 * N : nullptr, m0, rsc);
 }
 
-static int num_cus() { return 256; }
+// ---------------------------------------------------------------------------------------
+// Host dispatch
+// ---------------------------------------------------------------------------------------
+// One GEMM call: what every plan's launcher needs besides its template parameters.
+struct GemmArgs {
+  const bf16* X;
+  long ldx;
+  const bf16* W;
+  long ldw;        // K for a pack_w256 weight
+  int M, N, K, epi;
+  const bf16* bias;
+  bf16* out;
+  long ldo;
+  float* ws;       // [kCounterBytes reserved head | sk x M x N f32 partials]; read when sk > 1
+  RowScale rsc;
+  bool row_scale;  // the caller passed `rsc`: only kinds with a row-scale epilogue may run
+};
+using GemmLauncher = void (*)(const GemmArgs&, int sk, hipStream_t);
+constexpr RowScale kNoRowScale{nullptr, 0, 0.f, 0.f};
 
-// Workspace layout: [kCounterBytes reserved head | SK x M x N f32 partials].
-static float* splitk_part(float* ws) { return ws + kCounterBytes / sizeof(float); }
-
-
-
-template <int MT, int NT, int WK>
-static void run_skinny(const bf16* X, long ldx, const bf16* W, long ldw, int M, int N, int K,
-                       int epi, const bf16* bias, bf16* out, long ldo, float* ws, int sk,
-                       hipStream_t stream) {
-  dim3 grid(N / (16 * NT * (4 / WK)), sk);
-  gemm_skinny_kernel<MT, NT, WK><<<grid, kSkThreads, 0, stream>>>(
-      X, ldx, W, ldw, M, N, K, epi, bias, out, ldo, sk > 1 ? splitk_part(ws) : nullptr);
-}
+static float* slabs(const GemmArgs& a, int sk) { return sk > 1 ? a.ws + kCounterBytes / sizeof(float) : nullptr; }
 
 static void init_nt_policy() {
   static bool done = false;
@@ -1599,125 +1603,79 @@ static void init_nt_policy() {
   if (e && e[0] == '0') (void)hipMemcpyToSymbol(HIP_SYMBOL(g_tile_w_nt), &zero, sizeof(int));
 }
 
-template <int BM, int BN, int WMW, int STAGES, bool PACKW = false>
-static void run_tile(const bf16* X, long ldx, const bf16* W, long ldw, int M, int N, int K,
-                     int epi, const bf16* bias, bf16* out, long ldo, float* ws, int sk,
-                     hipStream_t stream, const RowScale& rsc) {
+// Every kernel launch of this file. 64 KiB of dynamic LDS or more is opted into once per kernel
+// (`lds` is a constant of each instantiation, so the first call's value is every call's).
+template <auto Kernel, class... A>
+static void launch(dim3 grid, int block, size_t lds, hipStream_t stream, A... args) {
+  static const bool opted_in = [lds] {
+    if (lds >= 65536)
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)lds);
+    return true;
+  }();
+  (void)opted_in;
   init_nt_policy();
-  const int tiles = ((M + BM - 1) / BM) * (N / BN);
-  const size_t lds = (size_t)STAGES * (BM + BN) * kBK * 2;
-  const dim3 grid(tiles, sk);
-  static bool attr_set = false;  // > 64 KiB of dynamic LDS must be opted into once per kernel
-  if (!attr_set && lds > 65536) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tile_kernel<BM, BN, WMW, STAGES, false, PACKW>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  gemm_tile_kernel<BM, BN, WMW, STAGES, false, PACKW><<<grid, kTileThreads, lds, stream>>>(
-      X, ldx, W, PACKW ? (long)K : ldw, M, N, K, epi, bias, out, ldo, sk > 1 ? splitk_part(ws) : nullptr,
-      nullptr, nullptr, nullptr, 0, rsc);
+  Kernel<<<grid, block, lds, stream>>>(args...);
 }
 
-// `nwide` column tiles of BNW then `nnarrow` of BNN (gemm_tile_mixed_kernel); the dynamic LDS is
-// per launch, so it is sized for the wide tile.
+// The dense kernels share their first twelve parameters; `tail` is what follows them.
+template <auto Kernel, class... T>
+static void launch_dense(dim3 grid, int block, size_t lds, const GemmArgs& a, int sk, hipStream_t stream, T... tail) {
+  launch<Kernel>(grid, block, lds, stream, a.X, a.ldx, a.W, a.ldw, a.M, a.N, a.K, a.epi, a.bias, a.out, a.ldo,
+                 slabs(a, sk), tail...);
+}
+
+static int tiles_of(const GemmArgs& a, int bm, int bn) { return ((a.M + bm - 1) / bm) * (a.N / bn); }
+
+template <int MT, int NT, int WK>
+static void run_skinny(const GemmArgs& a, int sk, hipStream_t stream) {
+  launch_dense<gemm_skinny_kernel<MT, NT, WK>>(dim3(a.N / (16 * NT * (4 / WK)), sk), kSkThreads, 0, a, sk, stream);
+}
+
+template <int BM, int BN, int WMW, int STAGES, bool PACKW>
+static void run_tile(const GemmArgs& a, int sk, hipStream_t stream) {
+  launch_dense<gemm_tile_kernel<BM, BN, WMW, STAGES, false, PACKW>>(
+      dim3(tiles_of(a, BM, BN), sk), kTileThreads, (size_t)STAGES * (BM + BN) * kBK * 2, a, sk, stream, nullptr,
+      nullptr, nullptr, 0, a.rsc);
+}
+
+// N / (BNW + BNN) column tiles of BNW then as many of BNN (gemm_tile_mixed_kernel); the dynamic
+// LDS is per launch, so it is sized for the wide tile.
 template <int BM, int BNW, int WMWW, int BNN, int WMWN, int STAGES, bool PACKW>
-static void run_tile_mixed(const bf16* X, long ldx, const bf16* W, long ldw, int M, int N, int K,
-                           int epi, const bf16* bias, bf16* out, long ldo, float* ws, int sk,
-                           hipStream_t stream, const RowScale& rsc, int nwide, int nnarrow) {
-  init_nt_policy();
-  const int mtiles = (M + BM - 1) / BM;
-  const size_t lds = (size_t)STAGES * (BM + BNW) * kBK * 2;
-  const dim3 grid((nwide + nnarrow) * mtiles, sk);
-  static bool attr_set = false;
-  if (!attr_set && lds > 65536) {
-    hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&gemm_tile_mixed_kernel<BM, BNW, WMWW, BNN, WMWN, STAGES, PACKW>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  gemm_tile_mixed_kernel<BM, BNW, WMWW, BNN, WMWN, STAGES, PACKW><<<grid, kTileThreads, lds, stream>>>(
-      X, ldx, W, PACKW ? (long)K : ldw, M, N, K, epi, bias, out, ldo, sk > 1 ? splitk_part(ws) : nullptr, nwide,
-      rsc);
+static void run_tile_mixed(const GemmArgs& a, int sk, hipStream_t stream) {
+  const int npair = a.N / (BNW + BNN), mtiles = (a.M + BM - 1) / BM;
+  launch_dense<gemm_tile_mixed_kernel<BM, BNW, WMWW, BNN, WMWN, STAGES, PACKW>>(
+      dim3(2 * npair * mtiles, sk), kTileThreads, (size_t)STAGES * (BM + BNW) * kBK * 2, a, sk, stream, npair, a.rsc);
 }
 
 template <int BM, int BN, int NWM, int NWN, int SW>
-static void run_dec(const bf16* X, long ldx, const bf16* W, long ldw, int M, int N, int K,
-                    int epi, const bf16* bias, bf16* out, long ldo, float* ws, int sk,
-                    hipStream_t stream, const RowScale& rsc) {
-  init_nt_policy();
-  const int tiles = ((M + BM - 1) / BM) * (N / BN);
+static void run_dec(const GemmArgs& a, int sk, hipStream_t stream) {
   constexpr size_t lds = (size_t)(3 * BM + SW * BN) * kBK * 2;
   static_assert(lds <= 160 * 1024, "decode GEMM rings exceed the 160 KiB LDS");
-  static bool attr_set = false;
-  if (!attr_set && lds > 65536) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_dec_kernel<BM, BN, NWM, NWN, SW>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  const dim3 grid(tiles, sk);
-  gemm_dec_kernel<BM, BN, NWM, NWN, SW><<<grid, NWM * NWN * 64, lds, stream>>>(
-      X, ldx, W, ldw, M, N, K, epi, bias, out, ldo, sk > 1 ? splitk_part(ws) : nullptr, rsc);
+  launch_dense<gemm_dec_kernel<BM, BN, NWM, NWN, SW>>(dim3(tiles_of(a, BM, BN), sk), NWM * NWN * 64, lds, a, sk,
+                                                      stream, a.rsc);
 }
 
-static void run_big8(const bf16* X, long ldx, const bf16* W, long ldw, int M, int N, int K,
-                     int epi, const bf16* bias, bf16* out, long ldo, float* ws, int sk, hipStream_t stream) {
-  static bool attr = false;
-  if (!attr) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_big8_kernel<false>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, kB8LdsBytes);
-    attr = true;
-  }
-  const int tiles = ((M + 255) / 256) * (N / 256);
-  dim3 grid(tiles, sk);
-  float* part = sk > 1 ? splitk_part(ws) : nullptr;
-  gemm_big8_kernel<false><<<grid, kB8Threads, kB8LdsBytes, stream>>>(X, ldx, W, ldw, M, N, K, epi, bias, out, ldo, part);
+static void run_big8(const GemmArgs& a, int sk, hipStream_t stream) {
+  launch_dense<gemm_big8_kernel<false>>(dim3(tiles_of(a, 256, 256), sk), kB8Threads, kB8LdsBytes, a, sk, stream,
+                                        nullptr, nullptr, nullptr, 0);
 }
 
-static void run_big4(const bf16* X, long ldx, const bf16* W, long ldw, int M, int N, int K,
-                     int epi, const bf16* bias, bf16* out, long ldo, float* ws, int sk, hipStream_t stream) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_big4_kernel<false>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, kB4LdsBytes);
-    attr_set = true;
-  }
-  dim3 grid(((M + 255) / 256) * (N / 256), sk);
-  float* part = sk > 1 ? splitk_part(ws) : nullptr;
-  gemm_big4_kernel<false><<<grid, kB4Threads, kB4LdsBytes, stream>>>(X, ldx, W, ldw, M, N, K, epi, bias, out, ldo, part);
+static void run_big4(const GemmArgs& a, int sk, hipStream_t stream) {
+  launch_dense<gemm_big4_kernel<false>>(dim3(tiles_of(a, 256, 256), sk), kB4Threads, kB4LdsBytes, a, sk, stream,
+                                        nullptr, nullptr, nullptr, 0);
 }
 
-template <int BM, int BN, int SA, int SB, bool PK = false>
-static void run_mid4(const bf16* X, long ldx, const bf16* W, long ldw, int M, int N, int K, int epi,
-                     const bf16* bias, bf16* out, long ldo, float* ws, int sk, hipStream_t stream,
-                     const RowScale& rsc) {
-  using C = Mid4Cfg<BM, BN, SA, SB>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_mid4_kernel<BM, BN, SA, SB, PK>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-    attr_set = true;
-  }
-  dim3 grid(((M + BM - 1) / BM) * (N / BN), sk);
-  float* part = sk > 1 ? splitk_part(ws) : nullptr;
-  gemm_mid4_kernel<BM, BN, SA, SB, PK><<<grid, kMid4Threads, C::LDS, stream>>>(X, ldx, W, ldw, M, N, K, epi, bias,
-                                                                         out, ldo, part, rsc);
+template <int BM, int BN, int SA, int SB, bool PK>
+static void run_mid4(const GemmArgs& a, int sk, hipStream_t stream) {
+  launch_dense<gemm_mid4_kernel<BM, BN, SA, SB, PK>>(dim3(tiles_of(a, BM, BN), sk), kMid4Threads,
+                                                     Mid4Cfg<BM, BN, SA, SB>::LDS, a, sk, stream, a.rsc);
 }
 
-template <int BM, int BN, int SX, int SW, bool PK = false>
-static void run_mid8(const bf16* X, long ldx, const bf16* W, long ldw, int M, int N, int K, int epi,
-                     const bf16* bias, bf16* out, long ldo, float* ws, int sk, hipStream_t stream,
-                     const RowScale& rsc) {
-  init_nt_policy();
-  constexpr size_t lds = (size_t)MidCfg<BM, BN, SX, SW>::LDS;
-  static bool attr = false;
-  if (!attr) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_mid8_kernel<BM, BN, SX, SW, PK>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr = true;
-  }
-  const int tiles = ((M + BM - 1) / BM) * (N / BN);
-  gemm_mid8_kernel<BM, BN, SX, SW, PK><<<tiles * sk, kMidThreads, lds, stream>>>(
-      X, ldx, W, ldw, M, N, K, epi, bias, out, ldo, sk > 1 ? splitk_part(ws) : nullptr, sk, rsc);
+template <int BM, int BN, int SX, int SW, bool PK>
+static void run_mid8(const GemmArgs& a, int sk, hipStream_t stream) {
+  launch_dense<gemm_mid8_kernel<BM, BN, SX, SW, PK>>(dim3(tiles_of(a, BM, BN) * sk), kMidThreads,
+                                                     MidCfg<BM, BN, SX, SW>::LDS, a, sk, stream, sk, a.rsc);
 }
 
 // Plan selection, from the tools/bench_gemm.py sweep on MI355X (Llama-3-70B TP1/TP8 shapes,
@@ -1768,13 +1726,13 @@ static const std::vector<PlanOverride>& plan_overrides() {
   return v;
 }
 
-// Mixed-width tile plans {8, stages, 0, narrow width, BM, wide width, sk} (gemm_tile_mixed_kernel):
-// equal counts of wide and narrow column tiles, so N must be a multiple of the two widths' sum.
+// Mixed-width tile plans {kTileMixed, stages, 0, narrow width, BM, wide width, sk}: equal counts of
+// wide and narrow column tiles, so N must be a multiple of the two widths' sum.
 // BFLY_GEMM_MIXED_TILES / gemm_mixed_tiles_mode: 0 = never, 1 = the measured shapes, on the
 // packed weight only (kPackedTuned: on the row-major weight the mixed grid measured slower, 176
 // against 160 us for the Llama-3-70B gate/up), 2 = every decode tile plan of 128 columns whose N
 // splits, on either weight (tests, A/B runs).
-constexpr int kMixedWide = 128, kMixedNarrow = 96;
+constexpr int kMixedWide = 128, kMixedNarrow = 96;   // the one pair of widths with kernels
 static int g_mixed_mode = -1;
 
 int gemm_mixed_tiles_mode(int mode) {
@@ -1789,27 +1747,30 @@ int gemm_mixed_tiles_mode(int mode) {
 
 // Mode 2: the mixed twin of a decode tile plan of 128 columns, where N splits.
 static GemmPlan mixed_plan(const GemmPlan& p, int N) {
-  if (gemm_mixed_tiles_mode(-1) != 2 || p.kind != 1 || p.nt != 0 || p.bn != kMixedWide || p.bm > 64 || p.mt != 3 ||
-      N % (kMixedWide + kMixedNarrow) != 0)
+  if (gemm_mixed_tiles_mode(-1) != 2 || p.kind != kTile || p.nt != 0 || p.bn != kMixedWide || p.bm > 64 ||
+      p.mt != 3 || N % (kMixedWide + kMixedNarrow) != 0)
     return p;
-  return GemmPlan{8, 3, 0, kMixedNarrow, p.bm, kMixedWide, p.sk};
+  return GemmPlan{kTileMixed, 3, 0, kMixedNarrow, p.bm, kMixedWide, p.sk};
+}
+
+// Token-count buckets of the sweep: M uses the table entries of its bucket; 0 above the last.
+static int bucket_of(int M) {
+  for (int b : {1, 16, 32, 64, 128, 256, 512})
+    if (b >= M) return b;
+  return 0;
 }
 
 GemmPlan plan_gemm(int M, int N, int K) {
-  static const int kBuckets[] = {1, 16, 32, 64, 128, 256, 512};
-  int bucket = 0;
-  for (int b : kBuckets)
-    if (b >= M) { bucket = b; break; }
+  const int bucket = bucket_of(M);
   for (const PlanOverride& o : plan_overrides())
     if (o.N == N && o.K == K && o.M == bucket) return o.p;
   if (!tuned_enabled()) return mixed_plan(plan_gemm_heuristic(M, N, K), N);
-  // token-count buckets of the sweep: M uses the entry of its bucket, or the heuristic plan
-  // when the sweep found nothing better there
+  // the entry of M's bucket, or the heuristic plan when the sweep found nothing better there
   if (bucket == 0) return plan_gemm_heuristic(M, N, K);
   for (const TunedPlan& t : kTuned)
     if (t.N == N && t.K == K && t.M == bucket)   // 256x256 entries (swept on big8) run big4:
-      return t.kind == 4 ? GemmPlan{6, 0, 0, 0, 256, 256, t.sk}   // >= big8 at every swept M / sk
-                         : GemmPlan{t.kind, t.mt, t.nt, t.wk, t.bm, t.bn, t.sk};
+      return t.kind == kBig8 ? GemmPlan{kBig4, 0, 0, 0, 256, 256, t.sk}   // >= big8 at every swept M / sk
+                             : GemmPlan{t.kind, t.mt, t.nt, t.wk, t.bm, t.bn, t.sk};
   return mixed_plan(plan_gemm_heuristic(M, N, K), N);
 }
 
@@ -1820,7 +1781,7 @@ static GemmPlan plan_gemm_heuristic(int M, int N, int K) {
   // register-streaming kernel: GEMV-like M, and short-K shapes (row-parallel projections
   // after TP splits K) where the LDS pipeline cannot fill before the K loop ends
   if (skinny_ok && (M <= 4 || (M <= 64 && K <= 1024))) {
-    p.kind = 0;
+    p.kind = kSkinny;
     p.mt = (M + 15) / 16;
     const bool long_k = K > 4096;
     p.nt = M <= 4 ? (long_k ? 4 : 2) : 2;   // even: the SiLU epilogue pairs gate/up groups
@@ -1837,7 +1798,7 @@ static GemmPlan plan_gemm_heuristic(int M, int N, int K) {
     // PF at M = 8192 on the 70B projections, 6-10 % over the 8-phase gemm_big8_kernel and ahead
     // of it at M = 256-2048 too, profiles/r5_gemm_big4/); split K only when the tile grid cannot
     // fill the 256 CUs
-    p.kind = 6;
+    p.kind = kBig4;
     p.mt = 0;
     p.bm = p.bn = 256;
     const int tiles = ((M + 255) / 256) * (N / 256);
@@ -1846,8 +1807,8 @@ static GemmPlan plan_gemm_heuristic(int M, int N, int K) {
     p.sk = sk;
     return p;
   }
-  p.kind = 1;
-  p.mt = M >= 512 ? 2 : 3;   // tile plans: `mt` = pipeline depth (K-tiles in flight + 1)
+  p.kind = kTile;
+  p.mt = M >= 512 ? 2 : 3;
   if (M <= 16) { p.bm = 16; p.wk = 1; }
   else if (M <= 32) { p.bm = 32; p.wk = 1; }
   else if (M <= 64) { p.bm = 64; p.wk = 2; }
@@ -1865,179 +1826,208 @@ static size_t plan_ws_bytes(const GemmPlan& p, int M, int N) {
   return p.sk > 1 ? kCounterBytes + (size_t)p.sk * M * N * sizeof(float) : 0;
 }
 
-// Enough for the tuned plan and for the heuristic plan it may fall back to (below).
+// The plan splits K and the caller's workspace cannot hold its slabs.
+static bool ws_short(const GemmPlan& p, int M, int N, const float* ws, size_t ws_bytes) {
+  return p.sk > 1 && (ws == nullptr || ws_bytes < plan_ws_bytes(p, M, N));
+}
+
+// Enough for the tuned plan and for the heuristic plan it may fall back to (select_plan).
 size_t gemm_workspace_bytes(int M, int N, int K) {
   const size_t a = plan_ws_bytes(plan_gemm(M, N, K), M, N);
   const size_t b = plan_ws_bytes(plan_gemm_heuristic(M, N, K), M, N);
   return a > b ? a : b;
 }
 
-// `dry`: validate only (the plan is supported for this shape/epilogue) without launching.
-static int run_plan(const GemmPlan& p, const bf16* X, long ldx, const bf16* W, long ldw, int M,
-                    int N, int K, int epi, const bf16* bias, bf16* out, long ldo, float* ws,
-                    hipStream_t stream, bool dry = false, bool defer = false,
-                    const RowScale* rs = nullptr, bool packed = false) {
-  const RowScale rsc = rs ? *rs : RowScale{nullptr, 0, 0.f, 0.f};
-  if (rs != nullptr && p.kind != 1 && p.kind != 3 && p.kind != 5 && p.kind != 7 && p.kind != 8) return -4;   // row scale: tile / ring / mid epilogues
-  if (epi == EPI_SILU_GATE && ((p.kind != 1 && p.kind != 8) || p.sk != 1)) return -4;   // gate: tile epilogue, no slabs
-  // packed (pack_w256) weights: `packed` alone picks the kernel that reads them (a plan's `nt`
-  // is no layout marker: the row-major entries run a tile plan that carries nt = 1 on the
-  // row-major kernel); the tile, mixed-tile and mid-M kernels have a packed form
-  if (packed && p.kind != 1 && p.kind != 5 && p.kind != 7 && p.kind != 8) return -5;
-  if (p.kind == 4) {
-    // 8-phase big tile: every split needs >= 2 K-tiles of 64
-    if (N % 256 != 0 || K % 64 != 0 || K / 64 < 2 * p.sk) return -1;
-    if (!dry) run_big8(X, ldx, W, ldw, M, N, K, epi, bias, out, ldo, ws, p.sk, stream);
-  } else if (p.kind == 7) {
-    // mid-M one-wave-per-SIMD tile: plan {7, SA (activation ring), SB (weight ring), 0, BM, BN, sk}
-    if (N % p.bn != 0 || K % 64 != 0 || K / 64 < p.sk) return -1;
-    bool done = false;
-#define MID4_CASE(BM_, BN_, SA_, SB_)                                                               \
-  if (!done && p.bm == BM_ && p.bn == BN_ && p.mt == SA_ && p.nt == SB_) {                          \
-    if (!dry && packed) run_mid4<BM_, BN_, SA_, SB_, true>(X, ldx, W, ldw, M, N, K, epi, bias, out, ldo, ws, p.sk, stream, rsc); \
-    else if (!dry) run_mid4<BM_, BN_, SA_, SB_>(X, ldx, W, ldw, M, N, K, epi, bias, out, ldo, ws, p.sk, stream, rsc); \
-    done = true;                                                                                   \
-  }
-    MID4_CASE(128, 128, 4, 6) MID4_CASE(128, 128, 3, 7) MID4_CASE(128, 128, 2, 8)
-    MID4_CASE(256, 128, 3, 4) MID4_CASE(256, 128, 2, 6) MID4_CASE(128, 256, 4, 3) MID4_CASE(128, 256, 2, 4)
+// The instantiated configurations, once per kind: a plan's launcher on the row-major or the
+// packed (pack_w256) weight, nullptr when no kernel was built for it. Validation and launch both
+// ask here, so a plan cannot validate without a kernel behind it. The kernels are emitted into
+// the code object in the order of these lists (a packed case before its row-major twin): a
+// reordering moves every kernel's address, which the measured plan table has not seen.
+static GemmLauncher find_mid4(const GemmPlan& p, bool packed) {
+#define MID4_CASE(BM_, BN_, SA_, SB_)                              \
+  if (p.bm == BM_ && p.bn == BN_ && p.mt == SA_ && p.nt == SB_) \
+    return packed ? &run_mid4<BM_, BN_, SA_, SB_, true> : &run_mid4<BM_, BN_, SA_, SB_, false>;
+  MID4_CASE(128, 128, 4, 6) MID4_CASE(128, 128, 3, 7) MID4_CASE(128, 128, 2, 8)
+  MID4_CASE(256, 128, 3, 4) MID4_CASE(256, 128, 2, 6) MID4_CASE(128, 256, 4, 3) MID4_CASE(128, 256, 2, 4)
 #undef MID4_CASE
-    if (!done) return -2;
-  } else if (p.kind == 6) {
-    // one-wave-per-SIMD 256x256 tile: every split needs >= 2 K-tiles of 64
-    if (N % 256 != 0 || K % 64 != 0 || K / 64 < 2 * p.sk) return -1;
-    if (!dry) run_big4(X, ldx, W, ldw, M, N, K, epi, bias, out, ldo, ws, p.sk, stream);
+  return nullptr;
+}
 
-  } else if (p.kind == 5) {
-    // mid-M 8-wave staggered GEMM: plan {5, SW (weight ring), SX (activation ring; 0 = SW), 0,
-    // BM, BN, sk}
-    if (N % p.bn != 0 || K % kBK != 0 || K / kBK < p.sk) return -1;
-    if (epi == EPI_SILU && p.bn * p.bm / 512 % 32 != 0) return -1;
-    const int sx = p.nt > 0 ? p.nt : p.mt;
-    bool done = false;
-#define MID_CASE(BM_, BN_, SX_, SW_)                                                              \
-  if (!done && p.bm == BM_ && p.bn == BN_ && sx == SX_ && p.mt == SW_) {                           \
-    if (!dry && packed) run_mid8<BM_, BN_, SX_, SW_, true>(X, ldx, W, ldw, M, N, K, epi, bias, out, ldo, ws, p.sk, stream, rsc); \
-    else if (!dry) run_mid8<BM_, BN_, SX_, SW_>(X, ldx, W, ldw, M, N, K, epi, bias, out, ldo, ws, p.sk, stream, rsc); \
-    done = true;                                                                                   \
-  }
-    MID_CASE(256, 128, 3, 3) MID_CASE(256, 128, 2, 6) MID_CASE(256, 128, 3, 4)
-    MID_CASE(128, 256, 3, 3) MID_CASE(128, 256, 2, 4)
-    MID_CASE(128, 128, 4, 4) MID_CASE(128, 128, 3, 3) MID_CASE(128, 128, 3, 6) MID_CASE(128, 128, 2, 8)
-    MID_CASE(128, 128, 2, 2)   // 64 KiB: two workgroups per CU
+static GemmLauncher find_mid8(const GemmPlan& p, bool packed) {
+  const int sx = p.nt > 0 ? p.nt : p.mt;
+#define MID_CASE(BM_, BN_, SX_, SW_)                            \
+  if (p.bm == BM_ && p.bn == BN_ && sx == SX_ && p.mt == SW_) \
+    return packed ? &run_mid8<BM_, BN_, SX_, SW_, true> : &run_mid8<BM_, BN_, SX_, SW_, false>;
+  MID_CASE(256, 128, 3, 3) MID_CASE(256, 128, 2, 6) MID_CASE(256, 128, 3, 4)
+  MID_CASE(128, 256, 3, 3) MID_CASE(128, 256, 2, 4)
+  MID_CASE(128, 128, 4, 4) MID_CASE(128, 128, 3, 3) MID_CASE(128, 128, 3, 6) MID_CASE(128, 128, 2, 8)
+  MID_CASE(128, 128, 2, 2)   // 64 KiB: two workgroups per CU
 #undef MID_CASE
-    if (!done) return -2;
-  } else if (p.kind == 3) {
-    // decode ring GEMM: plan {3, SW (weight ring depth), waves, waves along M, BM, BN, sk}
-    if (N % p.bn != 0 || K % kBK != 0 || K / kBK < p.sk * 2) return -1;
-    const int nwn = p.wk > 0 ? p.nt / p.wk : 0;
-    if (epi == EPI_SILU && (nwn <= 0 || (p.bn / nwn) % 32 != 0)) return -1;
-    bool done = false;
-#define DEC_CASE(BM_, BN_, NWM_, NWN_, SW_)                                                      \
-  if (!done && p.bm == BM_ && p.bn == BN_ && p.wk == NWM_ && p.nt == NWM_ * NWN_ && p.mt == SW_) { \
-    if (!dry) run_dec<BM_, BN_, NWM_, NWN_, SW_>(X, ldx, W, ldw, M, N, K, epi, bias, out, ldo, ws, p.sk, stream, rsc); \
-    done = true;                                                                                 \
-  }
-    DEC_CASE(128, 224, 8, 1, 4) DEC_CASE(128, 224, 8, 1, 3) DEC_CASE(128, 256, 8, 1, 3)
-    DEC_CASE(128, 256, 4, 2, 3) DEC_CASE(128, 128, 8, 1, 5) DEC_CASE(128, 128, 4, 2, 5)
-    DEC_CASE(128, 160, 8, 1, 4) DEC_CASE(128, 80, 8, 1, 6) DEC_CASE(128, 64, 8, 1, 8)
-    DEC_CASE(128, 64, 4, 2, 8) DEC_CASE(64, 128, 4, 2, 6) DEC_CASE(64, 256, 4, 2, 4)
-    DEC_CASE(64, 224, 4, 1, 4) DEC_CASE(64, 160, 4, 2, 5) DEC_CASE(64, 64, 4, 2, 8)
+  return nullptr;
+}
+
+static GemmLauncher find_dec(const GemmPlan& p) {
+#define DEC_CASE(BM_, BN_, NWM_, NWN_, SW_)                                                       \
+  if (p.bm == BM_ && p.bn == BN_ && p.wk == NWM_ && p.nt == NWM_ * NWN_ && p.mt == SW_) \
+    return &run_dec<BM_, BN_, NWM_, NWN_, SW_>;
+  DEC_CASE(128, 224, 8, 1, 4) DEC_CASE(128, 224, 8, 1, 3) DEC_CASE(128, 256, 8, 1, 3)
+  DEC_CASE(128, 256, 4, 2, 3) DEC_CASE(128, 128, 8, 1, 5) DEC_CASE(128, 128, 4, 2, 5)
+  DEC_CASE(128, 160, 8, 1, 4) DEC_CASE(128, 80, 8, 1, 6) DEC_CASE(128, 64, 8, 1, 8)
+  DEC_CASE(128, 64, 4, 2, 8) DEC_CASE(64, 128, 4, 2, 6) DEC_CASE(64, 256, 4, 2, 4)
+  DEC_CASE(64, 224, 4, 1, 4) DEC_CASE(64, 160, 4, 2, 5) DEC_CASE(64, 64, 4, 2, 8)
 #undef DEC_CASE
-    if (!done) return -2;
-  } else if (p.kind == 0) {
-    if (K % 128 != 0 || M > 16 * p.mt) return -1;
-    if (N % (16 * p.nt * (4 / p.wk)) != 0) return -1;
-    if (epi == EPI_SILU && p.nt % 2 != 0) return -1;
-    if (p.sk > 1 && N / (16 * p.nt * (4 / p.wk)) > kSplitCounters) return -1;
-    bool done = false;
-#define SK_CASE(MT_, NT_, WK_)                                                                   \
-  if (!done && p.mt == MT_ && p.nt == NT_ && p.wk == WK_) {                                       \
-    if (!dry) run_skinny<MT_, NT_, WK_>(X, ldx, W, ldw, M, N, K, epi, bias, out, ldo, ws, p.sk, stream); \
-    done = true;                                                                                  \
-  }
+  return nullptr;
+}
+
+static GemmLauncher find_skinny(const GemmPlan& p) {
+#define SK_CASE(MT_, NT_, WK_) \
+  if (p.mt == MT_ && p.nt == NT_ && p.wk == WK_) return &run_skinny<MT_, NT_, WK_>;
 #define SK_WK(MT_, NT_) SK_CASE(MT_, NT_, 1) SK_CASE(MT_, NT_, 2) SK_CASE(MT_, NT_, 4)
-    SK_WK(1, 1) SK_WK(1, 2) SK_WK(1, 4) SK_WK(2, 1) SK_WK(2, 2) SK_WK(2, 4)
-    SK_WK(3, 2) SK_WK(4, 1) SK_WK(4, 2) SK_WK(4, 4)
+  SK_WK(1, 1) SK_WK(1, 2) SK_WK(1, 4) SK_WK(2, 1) SK_WK(2, 2) SK_WK(2, 4)
+  SK_WK(3, 2) SK_WK(4, 1) SK_WK(4, 2) SK_WK(4, 4)
 #undef SK_WK
 #undef SK_CASE
-    if (!done) return -2;
-  } else if (p.kind == 8) {
-    // mixed-width tiles: {8, stages, 0, narrow width, BM, wide width, sk}; equal counts of the two
-    // widths (every CU's pair of workgroups then holds the same columns), so a shape whose N is
-    // no multiple of their sum has no solution and is refused
-    if (p.bn != kMixedWide || p.wk != kMixedNarrow || N % (p.bn + p.wk) != 0 || K % kBK != 0 || K / kBK < p.sk ||
-        p.sk < 1 || (packed && N % 256 != 0))
-      return -1;
-    if ((epi == EPI_SILU || epi == EPI_SILU_GATE) && (p.bn % 32 != 0 || p.wk % 32 != 0)) return -1;
-    const int npair = N / (p.bn + p.wk);
-    if (p.sk > 1 && 2L * npair * ((M + p.bm - 1) / p.bm) > kSplitCounters) return -1;
-    bool done = false;
-    const int st = p.mt > 0 ? p.mt : 3;
-#define MX_CASE(BM_, WMWW_, WMWN_)                                                                    \
-  if (!done && p.bm == BM_ && st == 3) {                                                              \
-    if (!dry && packed)                                                                               \
-      run_tile_mixed<BM_, kMixedWide, WMWW_, kMixedNarrow, WMWN_, 3, true>(X, ldx, W, ldw, M, N, K, epi, bias, out, \
-                                                                           ldo, ws, p.sk, stream, rsc, npair, npair); \
-    else if (!dry)                                                                                    \
-      run_tile_mixed<BM_, kMixedWide, WMWW_, kMixedNarrow, WMWN_, 3, false>(X, ldx, W, ldw, M, N, K, epi, bias, out, \
-                                                                            ldo, ws, p.sk, stream, rsc, npair, npair); \
-    done = true;                                                                                      \
-  }
-    // 64 rows: 2 x 2 waves on the wide tile, 4 x 1 on the narrow one (6 MFMA columns per wave);
-    // 16 / 32 rows: 1 x 4 waves, three of them own 32 columns of the narrow tile
-    MX_CASE(16, 1, 1) MX_CASE(32, 1, 1) MX_CASE(64, 2, 4)
+  return nullptr;
+}
+
+static GemmLauncher find_tile_mixed(const GemmPlan& p, bool packed) {
+  const int st = p.mt > 0 ? p.mt : 3;
+#define MX_CASE(BM_, WMWW_, WMWN_)                                                           \
+  if (p.bm == BM_ && st == 3)                                                                \
+    return packed ? &run_tile_mixed<BM_, kMixedWide, WMWW_, kMixedNarrow, WMWN_, 3, true>    \
+                  : &run_tile_mixed<BM_, kMixedWide, WMWW_, kMixedNarrow, WMWN_, 3, false>;
+  // 64 rows: 2 x 2 waves on the wide tile, 4 x 1 on the narrow one (6 MFMA columns per wave);
+  // 16 / 32 rows: 1 x 4 waves, three of them own 32 columns of the narrow tile
+  MX_CASE(16, 1, 1) MX_CASE(32, 1, 1) MX_CASE(64, 2, 4)
 #undef MX_CASE
-    if (!done) return -2;
-  } else if (p.kind == 1 && packed) {
-    // tile plan over a K-tile-blocked weight (pack_w256 layout): 16 / 32 / 64-row tiles of 128 /
-    // 256 columns (the packed layout only changes the weight stage's addresses, so every decode
-    // tile the row-major table picks, down to the B = 1 bucket, has its packed twin)
-    if (N % 256 != 0 || K % 64 != 0 || (p.bm != 16 && p.bm != 32 && p.bm != 64) || (p.bn != 128 && p.bn != 256) ||
-        K / kBK < p.sk)
-      return -1;
-    if (p.sk > 1 && (long)((M + p.bm - 1) / p.bm) * (N / p.bn) > kSplitCounters) return -1;
-    bool done = false;
-    const int st = p.mt > 0 ? p.mt : 2;
-#define TLP_CASE(BM_, BN_, WMW_, ST_)                                                                 \
-  if (!done && p.bm == BM_ && p.bn == BN_ && p.wk == WMW_ && st == ST_) {                             \
-    if (!dry) run_tile<BM_, BN_, WMW_, ST_, true>(X, ldx, W, ldw, M, N, K, epi, bias, out, ldo, ws, p.sk, stream, rsc); \
-    done = true;                                                                                      \
+  return nullptr;
+}
+
+static GemmLauncher find_tile(const GemmPlan& p, bool packed) {
+  const int st = p.mt > 0 ? p.mt : 2;
+#define TL_CASE(BM_, BN_, WMW_, ST_, PK_) \
+  if (p.bm == BM_ && p.bn == BN_ && p.wk == WMW_ && st == ST_) return &run_tile<BM_, BN_, WMW_, ST_, PK_>;
+#define TL_ST(BM_, BN_, WMW_, PK_) \
+  TL_CASE(BM_, BN_, WMW_, 2, PK_) TL_CASE(BM_, BN_, WMW_, 3, PK_) TL_CASE(BM_, BN_, WMW_, 4, PK_)
+  // 16 / 32 / 64-row tiles of 128 / 256 columns, on either weight: the packed layout only changes
+  // the weight stage's addresses, so every decode tile the row-major table picks, down to the
+  // B = 1 bucket, has its packed twin
+#define TL_DECODE(PK_)                                                                          \
+  TL_ST(16, 128, 1, PK_) TL_ST(16, 256, 1, PK_) TL_ST(32, 128, 1, PK_) TL_ST(32, 256, 1, PK_) \
+  TL_ST(64, 128, 1, PK_) TL_ST(64, 128, 2, PK_) TL_ST(64, 256, 1, PK_) TL_ST(64, 256, 2, PK_)
+  if (packed) {
+    TL_DECODE(true)
+    return nullptr;
   }
-#define TLP_ST(BM_, BN_, WMW_) TLP_CASE(BM_, BN_, WMW_, 2) TLP_CASE(BM_, BN_, WMW_, 3) TLP_CASE(BM_, BN_, WMW_, 4)
-    TLP_ST(16, 128, 1) TLP_ST(16, 256, 1) TLP_ST(32, 128, 1) TLP_ST(32, 256, 1)
-    TLP_ST(64, 128, 1) TLP_ST(64, 128, 2) TLP_ST(64, 256, 1) TLP_ST(64, 256, 2)
-#undef TLP_ST
-#undef TLP_CASE
-    if (!done) return -2;
-  } else {
-    if (N % p.bn != 0 || K % kBK != 0) return -1;
-    if (p.sk > 1 && (long)((M + p.bm - 1) / p.bm) * (N / p.bn) > kSplitCounters) return -1;
-    bool done = false;
-    const int st = p.mt > 0 ? p.mt : 2;   // tile plans reuse `mt` as the pipeline depth
-#define TL_CASE(BM_, BN_, WMW_, ST_)                                                            \
-  if (!done && p.bm == BM_ && p.bn == BN_ && p.wk == WMW_ && st == ST_) {                       \
-    if (!dry) run_tile<BM_, BN_, WMW_, ST_>(X, ldx, W, ldw, M, N, K, epi, bias, out, ldo, ws, p.sk, stream, rsc); \
-    done = true;                                                                                \
-  }
-#define TL_ST(BM_, BN_, WMW_) TL_CASE(BM_, BN_, WMW_, 2) TL_CASE(BM_, BN_, WMW_, 3) TL_CASE(BM_, BN_, WMW_, 4)
-    TL_ST(16, 128, 1) TL_ST(16, 256, 1) TL_ST(32, 128, 1) TL_ST(32, 256, 1)
-    TL_ST(64, 128, 1) TL_ST(64, 128, 2) TL_ST(64, 256, 1) TL_ST(64, 256, 2)
-    TL_ST(128, 128, 2) TL_ST(128, 256, 2)
-    // CU-balanced decode tiles: N/224 or N/160 tiles x split-K land on exactly 256 workgroups
-    // for the Llama-3-70B projections (gate/up 57344 = 256 x 224, QKV 10240 = 64 x 160)
-    TL_ST(64, 224, 4) TL_ST(64, 160, 4)
+  TL_DECODE(false)
+  TL_ST(128, 128, 2, false) TL_ST(128, 256, 2, false)
+  // CU-balanced decode tiles: N/224 or N/160 tiles x split-K land on exactly 256 workgroups
+  // for the Llama-3-70B projections (gate/up 57344 = 256 x 224, QKV 10240 = 64 x 160)
+  TL_ST(64, 224, 4, false) TL_ST(64, 160, 4, false)
+#undef TL_DECODE
 #undef TL_ST
 #undef TL_CASE
-    if (!done) return -2;
+  return nullptr;
+}
+
+// What a kind can do. A row scale needs the tile / ring / mid epilogues; the tile, mixed-tile and
+// mid-M kernels have a packed form; the MoE gate is in the tile epilogues.
+constexpr bool takes_row_scale(int kind) {
+  return kind == kTile || kind == kDec || kind == kMid8 || kind == kMid4 || kind == kTileMixed;
+}
+constexpr bool has_packed_form(int kind) {
+  return kind == kTile || kind == kMid8 || kind == kMid4 || kind == kTileMixed;
+}
+constexpr bool has_gate_epilogue(int kind) { return kind == kTile || kind == kTileMixed; }
+
+// The launcher of plan `p` for this shape, epilogue and weight layout, in `fn`; or why there is
+// none: -1 the shape does not fit the plan, -2 no kernel is instantiated for it, -4 the kind lacks
+// the epilogue or the row scale, -5 it has no packed form. `packed` alone picks the kernel that
+// reads a pack_w256 weight (a plan's `nt` is no layout marker: the row-major entries run a tile
+// plan that carries nt = 1 on the row-major kernel). GemmPlan's comment says what the fields hold.
+static int resolve_plan(const GemmPlan& p, int M, int N, int K, int epi, bool row_scale, bool packed,
+                        GemmLauncher& fn) {
+  if (row_scale && !takes_row_scale(p.kind)) return -4;
+  if (epi == EPI_SILU_GATE && (!has_gate_epilogue(p.kind) || p.sk != 1)) return -4;   // no slabs
+  if (packed && !has_packed_form(p.kind)) return -5;
+  switch (p.kind) {
+    case kBig8:
+    case kBig4:   // every split needs >= 2 K-tiles of 64
+      if (N % 256 != 0 || K % 64 != 0 || K / 64 < 2 * p.sk) return -1;
+      fn = p.kind == kBig8 ? &run_big8 : &run_big4;
+      break;
+    case kMid4:
+      if (N % p.bn != 0 || K % 64 != 0 || K / 64 < p.sk) return -1;
+      fn = find_mid4(p, packed);
+      break;
+    case kMid8:
+      if (N % p.bn != 0 || K % kBK != 0 || K / kBK < p.sk) return -1;
+      if (epi == EPI_SILU && p.bn * p.bm / 512 % 32 != 0) return -1;
+      fn = find_mid8(p, packed);
+      break;
+    case kDec: {
+      if (N % p.bn != 0 || K % kBK != 0 || K / kBK < p.sk * 2) return -1;
+      const int nwn = p.wk > 0 ? p.nt / p.wk : 0;
+      if (epi == EPI_SILU && (nwn <= 0 || (p.bn / nwn) % 32 != 0)) return -1;
+      fn = find_dec(p);
+      break;
+    }
+    case kSkinny:
+      if (K % 128 != 0 || M > 16 * p.mt) return -1;
+      if (N % (16 * p.nt * (4 / p.wk)) != 0) return -1;
+      if (epi == EPI_SILU && p.nt % 2 != 0) return -1;
+      if (p.sk > 1 && N / (16 * p.nt * (4 / p.wk)) > kSplitCounters) return -1;
+      fn = find_skinny(p);
+      break;
+    case kTileMixed: {
+      // equal counts of the two widths (every CU's pair of workgroups then holds the same
+      // columns), so a shape whose N is no multiple of their sum has no solution and is refused
+      if (p.bn != kMixedWide || p.wk != kMixedNarrow || N % (p.bn + p.wk) != 0 || K % kBK != 0 || K / kBK < p.sk ||
+          p.sk < 1 || (packed && N % 256 != 0))
+        return -1;
+      if ((epi == EPI_SILU || epi == EPI_SILU_GATE) && (p.bn % 32 != 0 || p.wk % 32 != 0)) return -1;
+      const int npair = N / (p.bn + p.wk);
+      if (p.sk > 1 && 2L * npair * ((M + p.bm - 1) / p.bm) > kSplitCounters) return -1;
+      fn = find_tile_mixed(p, packed);
+      break;
+    }
+    case kTile:
+    default:   // a kind without a name (the retired 2 among them) runs as a tile plan
+      if (packed) {
+        if (N % 256 != 0 || K % 64 != 0 || (p.bm != 16 && p.bm != 32 && p.bm != 64) ||
+            (p.bn != 128 && p.bn != 256) || K / kBK < p.sk)
+          return -1;
+      } else if (N % p.bn != 0 || K % kBK != 0) {
+        return -1;
+      }
+      if (p.sk > 1 && (long)((M + p.bm - 1) / p.bm) * (N / p.bn) > kSplitCounters) return -1;
+      fn = find_tile(p, packed);
+      break;
   }
-  if (p.sk > 1 && !dry && !defer) {
-    const int nout = epi == EPI_SILU ? N / 2 : N;
-    long total = (long)M * nout;
-    int grid = (int)((total + 255) / 256);
-    if (grid > 4096) grid = 4096;
-    gemm_splitk_reduce_kernel<<<grid, 256, 0, stream>>>(splitk_part(ws), p.sk, M, N, epi, bias,
-                                                         out, ldo);
-  }
+  return fn != nullptr ? 0 : -2;
+}
+
+// 0 when `p` has a kernel for this shape, epilogue and weight layout: resolve_plan without the launch.
+static int check_plan(const GemmPlan& p, int M, int N, int K, int epi, bool row_scale, bool packed) {
+  GemmLauncher fn = nullptr;
+  return resolve_plan(p, M, N, K, epi, row_scale, packed, fn);
+}
+
+static void splitk_reduce(const float* part, int sk, int M, int N, int epi, const bf16* bias, bf16* out, long ldo,
+                          hipStream_t stream) {
+  const long total = (long)M * (epi == EPI_SILU ? N / 2 : N);
+  const int grid = (int)((total + 255) / 256);
+  launch<gemm_splitk_reduce_kernel>(dim3(grid > 4096 ? 4096 : grid), 256, 0, stream, part, sk, M, N, epi, bias, out,
+                                    ldo);
+}
+
+// Check, launch, and reduce the split-K slabs unless the consumer will (`defer`).
+static int launch_plan(const GemmPlan& p, const GemmArgs& a, bool packed, bool defer, hipStream_t stream) {
+  GemmLauncher fn = nullptr;
+  const int rc = resolve_plan(p, a.M, a.N, a.K, a.epi, a.row_scale, packed, fn);
+  if (rc != 0) return rc;
+  fn(a, p.sk, stream);
+  if (p.sk > 1 && !defer) splitk_reduce(slabs(a, p.sk), p.sk, a.M, a.N, a.epi, a.bias, a.out, a.ldo, stream);
   return 0;
 }
 
@@ -2045,149 +2035,19 @@ int launch_gemm_plan(const GemmPlan& p, const bf16* X, long ldx, const bf16* W, 
                      int N, int K, int epi, const bf16* bias, bf16* out, long ldo, float* ws,
                      size_t ws_bytes, hipStream_t stream, bool packed) {
   if (M <= 0) return 0;
-  if (p.sk > 1 && (ws == nullptr || ws_bytes < kCounterBytes + (size_t)p.sk * M * N * sizeof(float)))
-    return -3;
-  return run_plan(p, X, ldx, W, packed ? (long)K : ldw, M, N, K, epi, bias, out, ldo, ws, stream, false, false,
-                  nullptr, packed);
+  if (ws_short(p, M, N, ws, ws_bytes)) return -3;
+  return launch_plan(p, {X, ldx, W, packed ? (long)K : ldw, M, N, K, epi, bias, out, ldo, ws, kNoRowScale, false},
+                     packed, false, stream);
 }
 
 int gemm_plan_check(const GemmPlan& p, int M, int N, int K, int epi, bool packed) {
-  return run_plan(p, nullptr, 0, nullptr, 0, M, N, K, epi, nullptr, nullptr, 0, nullptr, nullptr, true, false,
-                  nullptr, packed);
+  return check_plan(p, M, N, K, epi, false, packed);
 }
 
-// The plan for this call: the tuned/heuristic plan, or the heuristic one when a table entry
-// measured for another epilogue cannot run this one (e.g. odd skinny NT with SiLU).
-static GemmPlan select_plan(int M, int N, int K, int epi) {
-  GemmPlan p = plan_gemm(M, N, K);
-  if (run_plan(p, nullptr, 0, nullptr, 0, M, N, K, epi, nullptr, nullptr, 0, nullptr, nullptr, true) != 0)
-    p = plan_gemm_heuristic(M, N, K);
-  return p;
-}
-
-int gemm_rowscale_check(int M, int N, int K, int epi) {
-  if (M <= 0) return 0;
-  const RowScale probe{nullptr, 0, 0.f, 0.f};
-  return run_plan(select_plan(M, N, K, epi), nullptr, 0, nullptr, 0, M, N, K, epi, nullptr, nullptr, 0,
-                  nullptr, nullptr, true, false, &probe);
-}
-
-// Grouped expert GEMM (MoE): BM x 128 tile (BM = 64 or 128 rows per expert tile, chosen by
-// the caller from the expected rows per expert), 3-stage pipeline; grid = (max tiles, sk,
-// N / 128) with the device tile list deciding which workgroups run. sk > 1 splits K and
-// writes f32 slabs part[sk][slots][N] (consumed by moe_combine_slabs: the split-K reduce is
-// fused into the weighted combine) — decode-sized expert batches otherwise leave most CUs
-// idle on the down projection (N = hidden: 32 column tiles per expert tile).
-template <int BM>
-static int launch_grouped_bm(const bf16* X, long ldx, const bf16* W, long ldw, long w_estride, int N,
-                             int K, int epi, const int* rows, const int4* tiles, const int* count,
-                             int max_tiles, int slots, int sk, float* part, bf16* out, long ldo,
-                             hipStream_t stream) {
-  constexpr int BN = 128, WMW = 2, ST = 3;
-  const size_t lds = (size_t)ST * (BM + BN) * kBK * 2;
-  static bool attr_set = false;
-  if (!attr_set && lds > 65536) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tile_kernel<BM, BN, WMW, ST, true>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  dim3 grid(max_tiles, sk, N / BN);
-  gemm_tile_kernel<BM, BN, WMW, ST, true><<<grid, kTileThreads, lds, stream>>>(
-      X, ldx, W, ldw, slots, N, K, epi, nullptr, out, ldo, sk > 1 ? part : nullptr, rows,
-      tiles, count, w_estride);
-  return 0;
-}
-
-int launch_gemm_grouped(const bf16* X, long ldx, const bf16* W, long ldw, long w_estride, int N,
-                        int K, int epi, const int* rows, const int4* tiles, const int* count,
-                        int max_tiles, bf16* out, long ldo, hipStream_t stream, int bm, int slots,
-                        int sk, float* part) {
-  if (N % 128 != 0 || K % kBK != 0 || max_tiles <= 0) return -1;
-  if (epi != EPI_NONE && epi != EPI_SILU) return -1;
-  if (sk < 1 || sk > K / kBK || (sk > 1 && (part == nullptr || epi != EPI_NONE || slots <= 0))) return -2;
-  if (bm == 256) {
-    // prefill-scale expert batches: a 256x256 tile over the tile list, no split
-    if (N % 256 != 0 || K / 64 < 2 || sk != 1) return -2;
-    static bool attr = false;
-    if (!attr) {
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_big8_kernel<true>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, kB8LdsBytes);
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_big4_kernel<true>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, kB4LdsBytes);
-      attr = true;
-    }
-    dim3 grid(max_tiles * (N / 256), 1);
-    // the SwiGLU gate/up GEMM on big4, the down projection on big8: Mixtral 8x7B at 32k routed
-    // rows, gate/up 6.02-6.04 vs 6.35-6.40 ms, down 3.64-3.66 vs 3.19-3.20 ms
-    // (profiles/r5_gemm_big4/grouped_moe_per_gemm.log)
-    if (epi == EPI_SILU)
-      gemm_big4_kernel<true><<<grid, kB4Threads, kB4LdsBytes, stream>>>(
-          X, ldx, W, ldw, max_tiles * 256, N, K, epi, nullptr, out, ldo, nullptr, rows, tiles, count, w_estride);
-    else
-      gemm_big8_kernel<true><<<grid, kB8Threads, kB8LdsBytes, stream>>>(
-          X, ldx, W, ldw, max_tiles * 256, N, K, epi, nullptr, out, ldo, nullptr, rows, tiles, count, w_estride);
-    return 0;
-  }
-  if (bm == 128)
-    return launch_grouped_bm<128>(X, ldx, W, ldw, w_estride, N, K, epi, rows, tiles, count, max_tiles,
-                                  slots, sk, part, out, ldo, stream);
-  if (bm == 64)
-    return launch_grouped_bm<64>(X, ldx, W, ldw, w_estride, N, K, epi, rows, tiles, count, max_tiles,
-                                 slots, sk, part, out, ldo, stream);
-  return -3;
-}
-
-int gemm_check(int M, int N, int K, int epi) {
-  if (M <= 0) return 0;
-  return run_plan(select_plan(M, N, K, epi), nullptr, 0, nullptr, 0, M, N, K, epi, nullptr, nullptr,
-                  0, nullptr, nullptr, true);
-}
-
-int launch_gemm_deferred(const bf16* X, long ldx, const bf16* W, long ldw, int M, int N, int K,
-                         bf16* out, long ldo, float* ws, size_t ws_bytes, hipStream_t stream,
-                         const RowScale* rs) {
-  if (M <= 0) return 1;
-  GemmPlan p = select_plan(M, N, K, EPI_NONE);
-  if (p.sk > 1 && (ws == nullptr || ws_bytes < kCounterBytes + (size_t)p.sk * M * N * sizeof(float)))
-    p.sk = 1;
-  const bool defer = p.sk > 1;
-  const int rc = run_plan(p, X, ldx, W, ldw, M, N, K, EPI_NONE, nullptr, out, ldo, ws, stream,
-                          false, defer, rs);
-  if (rc != 0) return rc;
-  return defer ? p.sk : 1;
-}
-
-size_t gemm_slab_offset_floats() { return kCounterBytes / sizeof(float); }
-
-void launch_splitk_reduce(const float* part, int sk, int M, int N, bf16* out, long ldo,
-                          hipStream_t stream) {
-  long total = (long)M * N;
-  int grid = (int)((total + 255) / 256);
-  if (grid > 4096) grid = 4096;
-  gemm_splitk_reduce_kernel<<<grid, 256, 0, stream>>>(part, sk, M, N, EPI_NONE, nullptr, out, ldo);
-}
-
-int launch_gemm(const bf16* X, long ldx, const bf16* W, long ldw, int M, int N, int K, int epi,
-                const bf16* bias, bf16* out, long ldo, float* ws, size_t ws_bytes,
-                hipStream_t stream, const RowScale* rs) {
-  if (M <= 0) return 0;
-  GemmPlan p = select_plan(M, N, K, epi);
-  if (p.sk > 1 && (ws == nullptr || ws_bytes < kCounterBytes + (size_t)p.sk * M * N * sizeof(float)))
-    p.sk = 1;
-  return run_plan(p, X, ldx, W, ldw, M, N, K, epi, bias, out, ldo, ws, stream, false, false, rs);
-}
-
-// Decode GEMM over a K-tile-blocked copy of the weight (layout [N/256][K/64][256][64], made
-// once by the engine when HBM allows, models/transformer.pack_decode_weights): the plan the
-// row-major weight would run (16 / 32 / 64-row tiles and the mid-M kernels of kinds 5 / 7, with
-// their split-K; EPI_SILU_GATE: the gate plan) on the packed copy. Each 128-row weight stage is then one 16 KiB run of memory instead of 128
-// runs of 128 B a row pitch apart: the Llama-3-70B gate/up GEMM at M = 64 in 145 against
-// 158 us, bitwise the same result (tools/packed_probe.py). Returns < 0 (nothing launched)
-// when the plan for this shape is not such a tile plan: the caller then uses the row-major
-// weight. `dry`: only report whether it applies.
 // Packed-weight plans that differ from the row-major table's (tools/packed_probe.py --sweep,
-// isolated, weights rotating through HBM; profiles/r6_packed/sweep_m64.jsonl): kind -1 = keep
-// this shape on the row-major weight (its row-major plan is faster than any packed one).
+// isolated, weights rotating through HBM; profiles/r6_packed/sweep_m64.jsonl): kKeepRowMajor =
+// keep this shape on the row-major weight (its row-major plan is faster than any packed one).
+constexpr int kKeepRowMajor = -1;
 struct PackedTuned { int N, K, M; GemmPlan p; };
 static const PackedTuned kPackedTuned[] = {
     {8192, 8192, 64, {1, 3, 1, 2, 64, 128, 4}},   // 70B O: 29.3 us vs 32.7 (row-major table plan, split-K 8)
@@ -2196,75 +2056,175 @@ static const PackedTuned kPackedTuned[] = {
     // (profiles/balanced_tiles/README.md). Not Mixtral 8x7B's dense expert gate/up (229376 x 4096,
     // 1792 tiles -> 1024 + 1024): its step measured slower with it, 17.70 -> 18.10 ms
     {57344, 8192, 64, {8, 3, 0, kMixedNarrow, 64, kMixedWide, 1}},
-    {4096, 4096, 1, {-1, 0, 0, 0, 0, 0, 0}},      // 8B O: row-major 13.7 us vs 14.2 packed at M = 64;
-    {4096, 4096, 16, {-1, 0, 0, 0, 0, 0, 0}},     // packing O / down measured 1-2 % slower per step
-    {4096, 4096, 32, {-1, 0, 0, 0, 0, 0, 0}},     // at B = 1 (kinds_b1_ab.log)
-    {4096, 4096, 64, {-1, 0, 0, 0, 0, 0, 0}},
+    {4096, 4096, 1, {kKeepRowMajor, 0, 0, 0, 0, 0, 0}},      // 8B O: row-major 13.7 us vs 14.2 packed at M = 64;
+    {4096, 4096, 16, {kKeepRowMajor, 0, 0, 0, 0, 0, 0}},     // packing O / down measured 1-2 % slower per step
+    {4096, 4096, 32, {kKeepRowMajor, 0, 0, 0, 0, 0, 0}},     // at B = 1 (kinds_b1_ab.log)
+    {4096, 4096, 64, {kKeepRowMajor, 0, 0, 0, 0, 0, 0}},
 };
 
-int launch_gemm_packed(const bf16* X, long ldx, const bf16* Wp, int M, int N, int K, int epi, bf16* out,
-                       long ldo, hipStream_t stream, const RowScale* rs, bool dry, float* ws, size_t ws_bytes,
-                       bool defer) {
-  if (M <= 0) return dry ? 0 : 1;
-  if (N % 256 != 0 || K % 64 != 0) return -1;
+// The gate epilogue's fallback: a tile plan without split-K (the expert GEMM is a weight stream
+// over >= 1792 column tiles, so it never needs one).
+static GemmPlan gate_plan(int M) {
+  const int bm = M <= 16 ? 16 : M <= 32 ? 32 : M <= 64 ? 64 : 128;
+  return GemmPlan{kTile, 3, 0, bm <= 32 ? 1 : 2, bm, 128, 1};
+}
+
+// The plan for this call: the override / tuned / heuristic plan (`packed`: a kPackedTuned entry
+// first, which may answer kKeepRowMajor), or the heuristic one when a table entry measured for
+// another epilogue cannot run this one (e.g. odd skinny NT with SiLU); for the gate epilogue on
+// the packed weight, the gate plan. Candidates are checked as row-major plans on either weight.
+static GemmPlan select_plan(int M, int N, int K, int epi, bool packed = false) {
   GemmPlan p = plan_gemm(M, N, K);
-  if (tuned_enabled() && plan_overrides().empty() && epi != EPI_SILU_GATE) {
-    static const int kB[] = {1, 16, 32, 64, 128, 256, 512};
-    int bucket = 0;
-    for (int b : kB)
-      if (b >= M) { bucket = b; break; }
+  if (packed && tuned_enabled() && plan_overrides().empty() && epi != EPI_SILU_GATE)
     for (const PackedTuned& t : kPackedTuned)
-      if (t.N == N && t.K == K && t.M == bucket) {
-        if (t.p.kind < 0) return -2;
-        if (t.p.kind == 8 && gemm_mixed_tiles_mode(-1) == 0) break;
-        if (run_plan(t.p, nullptr, 0, nullptr, 0, M, N, K, epi, nullptr, nullptr, 0, nullptr, nullptr, true) == 0)
-          p = t.p;
+      if (t.N == N && t.K == K && t.M == bucket_of(M)) {
+        if (t.p.kind == kKeepRowMajor) return t.p;
+        if (t.p.kind == kTileMixed && gemm_mixed_tiles_mode(-1) == 0) break;
+        if (check_plan(t.p, M, N, K, epi, false, false) == 0) p = t.p;
         break;
       }
+  if (check_plan(p, M, N, K, epi, false, false) != 0)
+    p = packed && epi == EPI_SILU_GATE ? gate_plan(M) : plan_gemm_heuristic(M, N, K);
+  return p;
+}
+
+int gemm_rowscale_check(int M, int N, int K, int epi) {
+  if (M <= 0) return 0;
+  return check_plan(select_plan(M, N, K, epi), M, N, K, epi, true, false);
+}
+
+// Grouped expert GEMM (MoE): BM x 128 tile (BM = 64 or 128 rows per expert tile, chosen by
+// the caller from the expected rows per expert), 3-stage pipeline; grid = (max tiles, sk,
+// N / 128) with the device tile list deciding which workgroups run. sk > 1 splits K and
+// writes f32 slabs part[sk][slots][N] (consumed by moe_combine_slabs: the split-K reduce is
+// fused into the weighted combine) — decode-sized expert batches otherwise leave most CUs
+// idle on the down projection (N = hidden: 32 column tiles per expert tile).
+int launch_gemm_grouped(const bf16* X, long ldx, const bf16* W, long ldw, long w_estride, int N,
+                        int K, int epi, const int* rows, const int4* tiles, const int* count,
+                        int max_tiles, bf16* out, long ldo, hipStream_t stream, int bm, int slots,
+                        int sk, float* part) {
+  if (N % 128 != 0 || K % kBK != 0 || max_tiles <= 0) return -1;
+  if (epi != EPI_NONE && epi != EPI_SILU) return -1;
+  if (sk < 1 || sk > K / kBK || (sk > 1 && (part == nullptr || epi != EPI_NONE || slots <= 0))) return -2;
+  const bf16* const no_bias = nullptr;
+  if (bm == 256) {
+    // prefill-scale expert batches: a 256x256 tile over the tile list, no split
+    if (N % 256 != 0 || K / 64 < 2 || sk != 1) return -2;
+    const dim3 grid(max_tiles * (N / 256), 1);
+    float* const no_part = nullptr;
+    // the SwiGLU gate/up GEMM on big4, the down projection on big8: Mixtral 8x7B at 32k routed
+    // rows, gate/up 6.02-6.04 vs 6.35-6.40 ms, down 3.64-3.66 vs 3.19-3.20 ms
+    // (profiles/r5_gemm_big4/grouped_moe_per_gemm.log)
+    if (epi != EPI_SILU)
+      launch<gemm_big8_kernel<true>>(grid, kB8Threads, kB8LdsBytes, stream, X, ldx, W, ldw, max_tiles * 256, N, K,
+                                     epi, no_bias, out, ldo, no_part, rows, tiles, count, w_estride);
+    else
+      launch<gemm_big4_kernel<true>>(grid, kB4Threads, kB4LdsBytes, stream, X, ldx, W, ldw, max_tiles * 256, N, K,
+                                     epi, no_bias, out, ldo, no_part, rows, tiles, count, w_estride);
+    return 0;
   }
-  if (epi != EPI_SILU_GATE &&
-      run_plan(p, nullptr, 0, nullptr, 0, M, N, K, epi, nullptr, nullptr, 0, nullptr, nullptr, true) != 0)
-    p = plan_gemm_heuristic(M, N, K);
-  if (epi == EPI_SILU_GATE &&
-      run_plan(p, nullptr, 0, nullptr, 0, M, N, K, epi, nullptr, nullptr, 0, nullptr, nullptr, true) != 0) {
-    const int bm = M <= 16 ? 16 : M <= 32 ? 32 : M <= 64 ? 64 : 128;
-    p = GemmPlan{1, 3, 0, bm <= 32 ? 1 : 2, bm, 128, 1};
-  }
-  // mid-M kernels (kinds 5 / 7): their weight DMA takes the packed layout as a template flag
-  const bool mid = (p.kind == 5 || p.kind == 7) && (p.bn == 128 || p.bn == 256);
-  const bool tile = (p.kind == 1 && (p.bn == 128 || p.bn == 256)) || p.kind == 8;
-  if (!mid && (!tile || (p.bm != 16 && p.bm != 32 && p.bm != 64))) return -2;
-  if (!dry && p.sk > 1 && (ws == nullptr || ws_bytes < kCounterBytes + (size_t)p.sk * M * N * sizeof(float)))
-    return -3;
-  if (dry)
-    return run_plan(p, nullptr, 0, nullptr, 0, M, N, K, epi, nullptr, nullptr, 0, nullptr, nullptr, true, false,
-                    nullptr, true);
-  const bool d = defer && p.sk > 1;
-  const int rc = run_plan(p, X, ldx, Wp, K, M, N, K, epi, nullptr, out, ldo, ws, stream, false, d, rs, true);
+  const auto tile = [&](auto bm_) {
+    constexpr int BM = decltype(bm_)::value, BN = 128, WMW = 2, ST = 3;
+    launch<gemm_tile_kernel<BM, BN, WMW, ST, true>>(dim3(max_tiles, sk, N / BN), kTileThreads,
+                                                    (size_t)ST * (BM + BN) * kBK * 2, stream, X, ldx, W, ldw, slots,
+                                                    N, K, epi, no_bias, out, ldo, sk > 1 ? part : nullptr, rows,
+                                                    tiles, count, w_estride, kNoRowScale);
+    return 0;
+  };
+  if (bm == 128) return tile(std::integral_constant<int, 128>{});
+  if (bm == 64) return tile(std::integral_constant<int, 64>{});
+  return -3;
+}
+
+int gemm_check(int M, int N, int K, int epi) {
+  if (M <= 0) return 0;
+  return check_plan(select_plan(M, N, K, epi), M, N, K, epi, false, false);
+}
+
+int launch_gemm_deferred(const bf16* X, long ldx, const bf16* W, long ldw, int M, int N, int K,
+                         bf16* out, long ldo, float* ws, size_t ws_bytes, hipStream_t stream,
+                         const RowScale* rs) {
+  if (M <= 0) return 1;
+  GemmPlan p = select_plan(M, N, K, EPI_NONE);
+  if (ws_short(p, M, N, ws, ws_bytes)) p.sk = 1;
+  const int rc = launch_plan(
+      p, {X, ldx, W, ldw, M, N, K, EPI_NONE, nullptr, out, ldo, ws, rs ? *rs : kNoRowScale, rs != nullptr}, false,
+      true, stream);
+  return rc != 0 ? rc : p.sk > 1 ? p.sk : 1;   // split count of the slabs left in the workspace, else 1
+}
+
+size_t gemm_slab_offset_floats() { return kCounterBytes / sizeof(float); }
+
+void launch_splitk_reduce(const float* part, int sk, int M, int N, bf16* out, long ldo,
+                          hipStream_t stream) {
+  splitk_reduce(part, sk, M, N, EPI_NONE, nullptr, out, ldo, stream);
+}
+
+int launch_gemm(const bf16* X, long ldx, const bf16* W, long ldw, int M, int N, int K, int epi,
+                const bf16* bias, bf16* out, long ldo, float* ws, size_t ws_bytes,
+                hipStream_t stream, const RowScale* rs) {
+  if (M <= 0) return 0;
+  GemmPlan p = select_plan(M, N, K, epi);
+  if (ws_short(p, M, N, ws, ws_bytes)) p.sk = 1;
+  return launch_plan(p, {X, ldx, W, ldw, M, N, K, epi, bias, out, ldo, ws, rs ? *rs : kNoRowScale, rs != nullptr},
+                     false, false, stream);
+}
+
+// Decode GEMM over a K-tile-blocked copy of the weight (layout [N/256][K/64][256][64], made
+// once by the engine when HBM allows, models/transformer.pack_decode_weights): the plan the
+// row-major weight would run (16 / 32 / 64-row tiles and the mid-M kernels, with their split-K;
+// EPI_SILU_GATE: the gate plan) on the packed copy. Each 128-row weight stage is then one 16 KiB
+// run of memory instead of 128 runs of 128 B a row pitch apart: the Llama-3-70B gate/up GEMM at
+// M = 64 in 145 against 158 us, bitwise the same result (tools/packed_probe.py). packed_plan
+// returns < 0 when the plan for this shape is not such a plan: the caller then uses the
+// row-major weight.
+static int packed_plan(int M, int N, int K, int epi, GemmPlan& p) {
+  if (N % 256 != 0 || K % 64 != 0) return -1;
+  p = select_plan(M, N, K, epi, true);
+  // mid-M kernels: their weight DMA takes the packed layout as a template flag
+  const bool mid = (p.kind == kMid8 || p.kind == kMid4) && (p.bn == 128 || p.bn == 256);
+  const bool tile = (p.kind == kTile && (p.bn == 128 || p.bn == 256)) || p.kind == kTileMixed;
+  if (!mid && (!tile || (p.bm != 16 && p.bm != 32 && p.bm != 64))) return -2;   // kKeepRowMajor too
+  return 0;
+}
+
+int gemm_packed_check(int M, int N, int K, int epi) {
+  if (M <= 0) return 0;
+  GemmPlan p{};
+  const int rc = packed_plan(M, N, K, epi, p);
+  return rc != 0 ? rc : check_plan(p, M, N, K, epi, false, true);
+}
+
+int launch_gemm_packed(const bf16* X, long ldx, const bf16* Wp, int M, int N, int K, int epi, bf16* out,
+                       long ldo, hipStream_t stream, const RowScale* rs, float* ws, size_t ws_bytes, bool defer) {
+  if (M <= 0) return 1;
+  GemmPlan p{};
+  int rc = packed_plan(M, N, K, epi, p);
   if (rc != 0) return rc;
-  return d ? p.sk : 1;     // split count of slabs left in the workspace (deferred), else 1
+  if (ws_short(p, M, N, ws, ws_bytes)) return -3;
+  const bool d = defer && p.sk > 1;
+  rc = launch_plan(p, {X, ldx, Wp, K, M, N, K, epi, nullptr, out, ldo, ws, rs ? *rs : kNoRowScale, rs != nullptr},
+                   true, d, stream);
+  return rc != 0 ? rc : d ? p.sk : 1;   // split count of slabs left in the workspace (deferred), else 1
 }
 
 // The dense MoE decode path's gate/up GEMM with the routing weight in its epilogue: one launch
 // and one pass over the [M, E * ffn] activation fewer per MoE layer (Mixtral 8x7B B = 64:
-// moe_gate_scale was 6.5 us per layer, profiles/r5_moe/mixtral_prefill_decode_trace.md). The
-// expert GEMM is a weight stream over >= 1792 column tiles, so the tile plan never splits K.
+// moe_gate_scale was 6.5 us per layer, profiles/r5_moe/mixtral_prefill_decode_trace.md).
 int launch_gemm_silu_gate(const bf16* X, long ldx, const bf16* W, long ldw, int M, int N, int K,
                           bf16* out, long ldo, const float* gates, int gld, int ge0, int gF,
                           hipStream_t stream) {
   if (M <= 0) return 0;
   if (gates == nullptr || gF <= 0 || gF % 16 != 0 || (N / 2) % gF != 0) return -5;
   GemmPlan p = plan_gemm(M, N, K);
-  if (run_plan(p, nullptr, 0, nullptr, 0, M, N, K, EPI_SILU_GATE, nullptr, nullptr, 0, nullptr, nullptr, true) != 0) {
-    const int bm = M <= 16 ? 16 : M <= 32 ? 32 : M <= 64 ? 64 : 128;
-    p = GemmPlan{1, 3, 0, bm <= 32 ? 1 : 2, bm, 128, 1};
-  }
-  RowScale rs{nullptr, 0, 0.f, 0.f};
+  if (check_plan(p, M, N, K, EPI_SILU_GATE, false, false) != 0) p = gate_plan(M);
+  RowScale rs = kNoRowScale;
   rs.gate = gates;
   rs.gld = gld;
   rs.ge0 = ge0;
   rs.gF = gF;
-  return run_plan(p, X, ldx, W, ldw, M, N, K, EPI_SILU_GATE, nullptr, out, ldo, nullptr, stream, false, false, &rs);
+  return launch_plan(p, {X, ldx, W, ldw, M, N, K, EPI_SILU_GATE, nullptr, out, ldo, nullptr, rs, true}, false, false,
+                     stream);
 }
 
 }  // namespace bfly
