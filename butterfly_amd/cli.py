@@ -3,6 +3,7 @@
   partition  --model llama3-70b --gpus 8 [--strategy tp2xpp4] [--objective latency] [--out plan.json]
              [--schedule RANK]   (that rank's decode-step communication program)
   generate   --model llama-tiny|CKPT_DIR --prompt "..." [--max-tokens N] [--plan auto|tp2] [--logprobs N]
+             [--presence-penalty X] [--frequency-penalty X] [--repetition-penalty X]
   serve      --model ... [--host 127.0.0.1 --port 8000]         (run under `launch` for N GPUs)
   bench      ...                                                  (forwards to bench.py)
   launch     -n 8 -- <program args...>                            one process per GPU
@@ -77,7 +78,8 @@ def cmd_generate(a) -> int:
               tokenizer=a.tokenizer)
     prompts = a.prompt or ["Hello"]
     params = SamplingParams(max_tokens=a.max_tokens, temperature=a.temperature, seed=a.seed, ignore_eos=True,
-                            logprobs=a.logprobs)
+                            logprobs=a.logprobs, presence_penalty=a.presence_penalty,
+                            frequency_penalty=a.frequency_penalty, repetition_penalty=a.repetition_penalty)
     # a restart is BFLY_RESTART (launch --max-restarts) or torchrun's TORCHELASTIC_RESTART_COUNT
     restart = max(int(os.environ.get("BFLY_RESTART", "0") or 0),
                   int(os.environ.get("TORCHELASTIC_RESTART_COUNT", "0") or 0))
@@ -208,6 +210,12 @@ def main(argv=None) -> int:
     g.add_argument("--no-graphs", action="store_true")
     g.add_argument("--logprobs", type=int, default=None, metavar="N",
                    help="print each generated token's log-probability and the N (0..20) most likely tokens")
+    g.add_argument("--presence-penalty", type=float, default=0.0,
+                   help="subtracted once from the logit of every token generated so far (-2..2)")
+    g.add_argument("--frequency-penalty", type=float, default=0.0,
+                   help="subtracted from a token's logit per occurrence among the generated tokens (-2..2)")
+    g.add_argument("--repetition-penalty", type=float, default=1.0,
+                   help="divides the positive (multiplies the negative) logits of prompt and generated tokens (> 0)")
     g.add_argument("--weight-dtype", default="auto", choices=["auto", "bf16", "fp8"],
                    help="dense projection weights: bf16, or fp8 (weight-only e4m3); auto = BFLY_WEIGHT_DTYPE")
     g.add_argument("--snapshot-dir", default=None,

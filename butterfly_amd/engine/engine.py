@@ -85,6 +85,16 @@ class StepOutput:
                                       # rows that did not ask hold None
 
 
+@dataclass
+class PenaltyState:
+    """Device token histories of the requests with a presence / frequency / repetition penalty
+    (ops.apply_penalties): hist [max_batch, max_seq_len padded to 4] int32, one row (slot) per
+    running request; `slot`: request id -> row, `free`: the rows nobody holds."""
+    hist: torch.Tensor
+    free: list
+    slot: dict = field(default_factory=dict)
+
+
 class LLMEngine:
     def __init__(self, cfg: ModelConfig, mesh: Mesh = Mesh(), engine_cfg: EngineConfig = EngineConfig(),
                  comm: Optional[Communicator] = None, device=None, stage_layers: Optional[list] = None,
@@ -213,6 +223,8 @@ class LLMEngine:
         d = self.model.dims
         self.sampler = Sampler(self.comm, cfg.vocab_size, d.vocab0, mesh.tp)
         self._lp = None      # device logprobs of the rows just sampled (_sample), until applied
+        self._pen: Optional[PenaltyState] = None   # allocated by the first penalised request
+        self._pen_src = None                       # (chunks, last, tokens_of) of the rows being sampled
         if self.device.type == "cuda":
             ops.reserve_workspace(self.device, max_tokens=max(engine_cfg.max_prefill_tokens, engine_cfg.max_batch),
                                   max_n=self._max_gemm_n(), max_k=self._max_gemm_k(),
@@ -315,6 +327,7 @@ class LLMEngine:
         if len(prompt) + params.max_tokens > self.ecfg.max_seq_len:
             raise ValueError(f"prompt ({len(prompt)}) + max_tokens ({params.max_tokens}) exceeds max_seq_len")
         self._check_logprobs(params)
+        self._check_penalties(params)
         self.requests[rid] = Request(rid, list(prompt), params, arrival=time.perf_counter())
         if self.cp_min and len(prompt) >= self.cp_min:
             self._cp_queue.append(rid)        # prefilled by the DP group together (_cp_step)
@@ -334,10 +347,80 @@ class LLMEngine:
             # only the last stage holds logits; a second boundary broadcast is not built
             raise ValueError("logprobs is not supported with pipeline parallelism (pp > 1)")
 
+    def _check_penalties(self, params: SamplingParams) -> None:
+        """Refuse out-of-range penalties; the first request that asks for one allocates the
+        device token histories (engines that never see one allocate nothing)."""
+        params.check_penalties()
+        if not params.needs_penalty:
+            return
+        if self.mesh.pp > 1:
+            # only the last stage holds logits, and only the first one the tokens
+            raise ValueError("penalties are not supported with pipeline parallelism (pp > 1)")
+        width = (self.ecfg.max_seq_len + 3) // 4 * 4
+        if width > ops.PENALTY_MAX_HISTORY:
+            raise ValueError(f"penalties need max_seq_len < 65536, got {self.ecfg.max_seq_len}")
+        if self._pen is None:
+            n = max(1, self.ecfg.max_batch)
+            self._pen = PenaltyState(torch.zeros(n, width, dtype=torch.int32, device=self.device),
+                                     list(range(n - 1, -1, -1)))
+
+    def _pen_release(self, rid: int) -> None:
+        """The request left the scheduler (finished or preempted): its history row is free.
+        Launches that read the row are already in the stream ahead of the next owner's writes."""
+        if self._pen is not None:
+            slot = self._pen.slot.pop(rid, None)
+            if slot is not None:
+                self._pen.free.append(slot)
+
+    def _penalise(self, logits: torch.Tensor, rids: list, chunks: int = 0, last=None, tokens_of=None) -> torch.Tensor:
+        """Penalised copy of `logits` for sampling (the raw ones stay for the logprobs), or
+        `logits` itself, with nothing launched, when no row asks. The last `chunks` rows were
+        sampled from a prompt chunk (first admission, recompute after preemption, a resumed
+        request, context-parallel prefill): such a row takes a history row if it has none and
+        the row is rewritten from the host's tokens (`tokens_of`, default the request's own).
+        A decode row's history is on the device already, but for its newest token: `last`
+        (device or host ids of the decode rows, as _first_stage_ids gives them; default the
+        host's last tokens), which the kernel counts and appends. Lengths come from the
+        value-free bookkeeping (prompt + n_gen), so no token value is waited for."""
+        reqs = [self.requests[r] for r in rids]
+        if not any(q.params.needs_penalty for q in reqs):
+            return logits
+        st = self._pen
+        R = len(rids)
+        nd = R - chunks
+        if tokens_of is None:
+            tokens_of = lambda r: self.requests[r].tokens      # noqa: E731
+        slots, lens, plens, newest = [-1] * R, [0] * R, [0] * R, [0] * R
+        for i, (r, q) in enumerate(zip(rids, reqs)):
+            if not q.params.needs_penalty:
+                continue
+            n = len(q.prompt) + q.n_gen
+            slot = st.slot.get(r)
+            if i >= nd:
+                toks = tokens_of(r)
+                if len(toks) < n:
+                    raise RuntimeError(f"request {r}: {len(toks)} tokens on the host, {n} in the sequence")
+                if slot is None:
+                    slot = st.slot[r] = st.free.pop()
+                st.hist[slot, :n].copy_(torch.tensor(toks[:n], dtype=torch.int32))
+                newest[i] = int(toks[n - 1])
+            elif slot is None:
+                raise RuntimeError(f"request {r}: a decode row without a token history")
+            elif not isinstance(last, torch.Tensor):
+                newest[i] = int(last[i]) if last is not None else int(q.tokens[-1])
+            slots[i], lens[i], plens[i] = slot, n, len(q.prompt)
+        meta = torch.tensor([slots, lens, plens, newest], dtype=torch.int32).to(self.device, non_blocking=True)
+        if isinstance(last, torch.Tensor) and nd:
+            meta[3, :nd].copy_(last[:nd])       # values the host does not have yet
+        params = ops.penalty_params([(q.params.repetition_penalty, q.params.frequency_penalty,
+                                      q.params.presence_penalty) for q in reqs]).to(self.device, non_blocking=True)
+        return self.sampler.penalise(logits, st.hist, meta, params)
+
     def _admit_resumed(self, req: Request) -> None:
         """Scheduler admission of a restored request (engine/state.py): its prompt plus the
         tokens it already generated are prefilled as one sequence, the rest is generated."""
         self._check_logprobs(req.params)
+        self._check_penalties(req.params)
         toks = req.tokens
         remaining = req.params.max_tokens - len(req.output)
         if len(toks) + remaining > self.ecfg.max_seq_len:
@@ -397,11 +480,11 @@ class LLMEngine:
     def _decode_sampling(self, rids: list) -> tuple:
         """Per-row temperatures / seeds of a decode plan for the graph's sampler (the values
         _sample_params gives the eager sampler), and whether some row needs the top-k / top-p
-        filter (sampled eagerly instead)."""
+        filter or a penalty (sampled eagerly instead)."""
         reqs = [self.requests[r] for r in rids]
         temps = np.asarray([max(0.0, q.params.temperature) for q in reqs], dtype=np.float32)
         seeds = np.asarray([(q.params.seed or r) * 1000003 + q.n_gen for q, r in zip(reqs, rids)], dtype=np.int64)
-        return temps, seeds, any(q.params.needs_filter for q in reqs)
+        return temps, seeds, any(q.params.needs_filter or q.params.needs_penalty for q in reqs)
 
     def _sample(self, logits: torch.Tensor, rids: list, graph_ids=None) -> torch.Tensor:
         """One token id per row (`graph_ids`: already sampled by the decode graph). When some
@@ -444,12 +527,25 @@ class LLMEngine:
                        (chosen[i], [(t, v) for t, v in zip(top_ids[i][:n], top_lp[i][:n]) if t >= 0]))
         return out
 
+    def _sample_rows(self, logits: torch.Tensor, rids: list, graph_ids=None, chunks: int = 0, last=None,
+                     tokens_of=None) -> torch.Tensor:
+        """`_sample`, told where the penalised rows' token histories come from (`_penalise`: the
+        last `chunks` rows are prompt-chunk rows whose host tokens `tokens_of` gives, `last` the
+        decode rows' newest tokens). Without it every row is a decode row of the synchronous
+        engine, whose host tokens are complete."""
+        self._pen_src = (chunks, last, tokens_of)
+        try:
+            return self._sample(logits, rids, graph_ids)
+        finally:
+            self._pen_src = None
+
     def _sample_eager(self, logits: torch.Tensor, rids: list) -> torch.Tensor:
         """Sample one token per row. With BFLY_NAN_CHECK the sampling kernel also flags rows
         with non-finite logits (id -1, no extra kernel, no host sync); a poisoned or corrupted
         step then raises in _apply_tokens instead of emitting garbage tokens."""
         logits = self._maybe_poison(logits)
         temps, seeds, params = self._sample_params(rids)
+        logits = self._penalise(logits, rids, *(self._pen_src or ()))
         return self.sampler.sample(logits, temps, seeds, params, check_finite=bool(self.nan_check))
 
     def _step(self) -> StepOutput:
@@ -488,6 +584,8 @@ class LLMEngine:
             self.metrics.set("prefix_cache_blocks", m.num_cached_blocks)
         if plan.preempted:
             self.metrics.inc("preempted_sequences", len(plan.preempted))
+            for r in plan.preempted:
+                self._pen_release(r)
         if self.mixed and plan.kind in (1, 3):
             # chunked prefill (+ decode rows): sample the decode rows and completed prompts
             fb, sample = self.runner.mixed_batch(plan, lambda r: self.requests[r].tokens)
@@ -496,7 +594,7 @@ class LLMEngine:
             logits = self.runner.run(fb)
             new = []
             if sample:
-                new = self._sample(logits, sample).tolist()
+                new = self._sample_rows(logits, sample, chunks=len(sample) - plan.num_decode).tolist()
             out = self._apply_tokens("prefill" if plan.kind == 1 else "mixed", sample, new, t0)
             out.prefill_tokens = int(sum(plan.prefill_lens))
             return out
@@ -504,7 +602,8 @@ class LLMEngine:
             fb = self.runner.prefill_batch(plan, lambda r: self.requests[r].tokens)
             fb.ep_tokens = ep_pad
             fb.ep_alltoall = self.mesh.ep > 1
-            tokens = self._run_stages(lambda h: self.runner.run(fb, h), fb.num_tokens, len(rids), rids)
+            tokens = self._run_stages(lambda h: self.runner.run(fb, h), fb.num_tokens, len(rids), rids,
+                                      chunks=len(rids))
             out = self._apply_tokens("prefill", rids, tokens.tolist(), t0)
             out.prefill_tokens = fb.num_tokens
             return out
@@ -561,7 +660,7 @@ class LLMEngine:
         self.metrics.inc("cp_prefill_tokens", mine)
         if rid is None:
             return StepOutput("cp-prefill", [], [], [], time.perf_counter() - t0, prefill_tokens=mine)
-        out = self._apply_tokens("prefill", [rid], self._sample(logits, [rid]).tolist(), t0)
+        out = self._apply_tokens("prefill", [rid], self._sample_rows(logits, [rid], chunks=1).tolist(), t0)
         out.prefill_tokens = mine
         return out
 
@@ -591,6 +690,7 @@ class LLMEngine:
             if reason:
                 req.finished, req.finish_reason, req.finish_time = True, reason, now
                 self.scheduler.finish(r)
+                self._pen_release(r)
                 finished.append(r)
         dt = time.perf_counter() - t0
         self.metrics.observe_step(kind, len(rids), dt)
@@ -659,12 +759,13 @@ class LLMEngine:
             elif e == "broadcast" and broadcast is not None:
                 broadcast(ins)
 
-    def _run_stages(self, fn, T: int, R: int, rids) -> torch.Tensor:
+    def _run_stages(self, fn, T: int, R: int, rids, chunks: int = 0) -> torch.Tensor:
         """Run this rank's pipeline stage on one batch; return sampled ids [R] (int32, on
         every rank of the replica). pp > 1: recv residual stream -> stage -> send, or sample
-        on the last stage; then the ids broadcast — as the step program lists them."""
+        on the last stage; then the ids broadcast — as the step program lists them. `chunks`:
+        the last `chunks` rows are sampled from prompt chunks (_penalise)."""
         if self.mesh.pp == 1:
-            return self._sample(fn(None), rids)
+            return self._sample_rows(fn(None), rids, chunks=chunks)
         m, res = self.model, {}
 
         def recv(ins):
@@ -810,6 +911,8 @@ class LLMEngine:
                 T = nd + int(sum(plan.prefill_lens))
             if plan.preempted:
                 self.metrics.inc("preempted_sequences", len(plan.preempted))
+                for r in plan.preempted:
+                    self._pen_release(r)
             self._inflight.append(PipePlan(k, g, plan, rids, T, list(plan.cow), seqs=seqs, ep_pad=ep_pad,
                                            ep_prefill=bool(any_prefill)))
             if s == 0:
@@ -877,6 +980,7 @@ class LLMEngine:
                 req.stopping = False
                 req.sched_done = True
                 self.scheduler.finish(r)
+                self._pen_release(r)
                 continue
             if r not in sampled:              # a prompt chunk that does not complete the prompt
                 continue
@@ -885,6 +989,7 @@ class LLMEngine:
             if req.n_gen >= req.params.max_tokens:
                 req.sched_done = True
                 self.scheduler.finish(r)
+                self._pen_release(r)
 
     def _apply_values(self, p: PipePlan, t0: float) -> StepOutput:
         """Token values of a plan advanced one tick ago: append them, detect stop tokens
@@ -926,6 +1031,7 @@ class LLMEngine:
                     else:
                         req.sched_done = True
                         self.scheduler.finish(r)
+                        self._pen_release(r)
         dt = time.perf_counter() - t0
         self.metrics.observe_step(p.kind, len(rids), dt)
         return StepOutput(p.kind, rids, toks, finished, dt, logprobs=kept if lps is not None else None)
@@ -1005,22 +1111,26 @@ class LLMEngine:
             if p.cow:
                 self.kv.copy_blocks(p.cow)
             if self.mixed and p.plan.kind in (1, 3):
-                fb, _ = self.runner.mixed_batch(p.plan, self._chunk_tokens(p))
+                state["tokens_of"] = self._chunk_tokens(p)
+                fb, _ = self.runner.mixed_batch(p.plan, state["tokens_of"])
                 fb.ep_tokens = p.ep_pad
                 fb.ep_alltoall = self.mesh.ep > 1
                 nd = p.plan.num_decode
                 if self.pp_first and nd:
-                    ids = self._first_stage_ids(p, list(p.plan.seq_ids)[:nd])
+                    ids = state["last"] = self._first_stage_ids(p, list(p.plan.seq_ids)[:nd])
                     if isinstance(ids, torch.Tensor):
                         fb.input_ids[:nd].copy_(ids)
                 out = self.runner.run(fb, h)
             elif p.plan.kind == 1:
-                fb = self.runner.prefill_batch(p.plan, self._chunk_tokens(p))
+                state["tokens_of"] = self._chunk_tokens(p)
+                fb = self.runner.prefill_batch(p.plan, state["tokens_of"])
                 fb.ep_tokens = p.ep_pad
                 fb.ep_alltoall = self.mesh.ep > 1
                 out = self.runner.run(fb, h)
             else:
                 ids = self._first_stage_ids(p) if self.pp_first else np.zeros(len(p.rids), dtype=np.int32)
+                if self.pp_first:
+                    state["last"] = ids
                 inp = self.runner.decode_inputs(p.plan, ids)
                 filtered = False
                 if self.pp_last and self.runner.sample_fn is not None:
@@ -1051,7 +1161,11 @@ class LLMEngine:
 
         def sample(mb, out):
             graph_ids = self.runner.last_ids if (p.plan.kind == 2 and not state.get("filtered")) else None
-            p.ids = self._sample(out, p.rids, graph_ids) if p.rids else \
+            # penalised rows (pp == 1: this stage built the plan's inputs): the chunk rows' host
+            # tokens and the decode rows' newest tokens, as the stage's input saw them
+            nd = 0 if p.plan.kind == 1 else p.plan.num_decode if p.plan.kind == 3 else len(p.rids)
+            p.ids = self._sample_rows(out, p.rids, graph_ids, chunks=len(p.rids) - nd, last=state.get("last"),
+                                      tokens_of=state.get("tokens_of")) if p.rids else \
                 torch.empty(0, dtype=torch.int32, device=self.device)
             p.lp = self._take_lp()
 

@@ -18,6 +18,7 @@ together. No candidate cap, no sort, no full-vocab gather:
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass, field
 from typing import Optional
 
@@ -36,10 +37,30 @@ class SamplingParams:
     ignore_eos: bool = False
     seed: Optional[int] = None
     logprobs: Optional[int] = None    # None = off; 0 = the generated token's; N = also the N most likely
+    presence_penalty: float = 0.0     # -2..2, subtracted once from every token generated so far
+    frequency_penalty: float = 0.0    # -2..2, subtracted per occurrence among the generated tokens
+    repetition_penalty: float = 1.0   # > 0, scales the logits of prompt and generated tokens
 
     @property
     def needs_filter(self) -> bool:
         return self.temperature > 0 and (self.top_k > 0 or self.top_p < 1.0)
+
+    @property
+    def needs_penalty(self) -> bool:
+        return self.presence_penalty != 0 or self.frequency_penalty != 0 or self.repetition_penalty != 1
+
+    def check_penalties(self) -> None:
+        """ValueError unless the three penalties are real numbers in their ranges."""
+        def number(v):
+            return not isinstance(v, bool) and isinstance(v, (int, float)) and math.isfinite(v)
+
+        for name in ("presence_penalty", "frequency_penalty"):
+            v = getattr(self, name)
+            if not number(v) or not -2.0 <= v <= 2.0:
+                raise ValueError(f"{name} must be a finite number in [-2, 2], got {v!r}")
+        v = self.repetition_penalty
+        if not number(v) or not v > 0:
+            raise ValueError(f"repetition_penalty must be a finite number > 0, got {v!r}")
 
 
 class Sampler:
@@ -81,6 +102,15 @@ class Sampler:
             return ops.logprobs_merge(rec.view(1, *rec.shape))
         allr = self.comm.all_gather(rec, "tp").view(self.tp, rec.shape[0], rec.shape[1])
         return ops.logprobs_merge(allr)
+
+    def penalise(self, logits: torch.Tensor, hist: torch.Tensor, meta: torch.Tensor,
+                 params: torch.Tensor) -> torch.Tensor:
+        """Presence / frequency / repetition penalties on this rank's shard, out of place
+        (ops.apply_penalties; the raw logits stay for `logprobs`). hist: the engine's device
+        token histories; meta [4, R] int32 = slots, lens, prompt_lens, newest tokens; params
+        [R, 4] f32. Each TP rank penalises its own columns: no collective."""
+        return ops.apply_penalties(self._local_valid(logits), hist, meta[0], meta[1], meta[2], meta[3], params,
+                                   vstart=self.vocab_start)
 
     def _merge(self, ids: torch.Tensor, scores: torch.Tensor) -> torch.Tensor:
         """Each vocab shard's winner -> the global winner: (score, id) pairs all-gathered over

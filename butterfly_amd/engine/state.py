@@ -19,7 +19,8 @@ replayed (cli.py `generate`).
 
 Format `butterfly-engine-state` v1 (JSON): {"format", "version", "model", "job", "dp_rank", "dp_size",
 "next_id", "steps_done", "requests": [{"rid", "prompt", "output", "params", "finished",
-"finish_reason"}]}. `params` may lack fields added later (`logprobs`: absent = off); the
+"finish_reason"}]}. `params` may lack fields added later (`logprobs`, the three penalties:
+absent = off; a resumed request's penalties see `prompt` as the prompt and `output` as generated); the
 log-probabilities themselves are not stored, so tokens generated before the snapshot report None
 after a resume. Tokens still in flight in the asynchronous pipeline (sampled, value not yet
 on the host) are not part of it: they are recomputed after the resume.

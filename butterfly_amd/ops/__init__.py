@@ -513,6 +513,34 @@ def logprobs_to_host(lp, non_blocking: bool = False):
     return _logprobs_views(host, R, n)
 
 
+PENALTY_MAX_HISTORY = 65535   # tokens of one history (penalties.hip counts in 16-bit halves)
+
+
+def penalty_params(params) -> torch.Tensor:
+    """Host rows [R, 4] f32 (rep, 1 / rep, freq, pres) for `apply_penalties` from (repetition,
+    frequency, presence) triples; the f32 reciprocal is taken here, on the host."""
+    return ref.penalty_params(params)
+
+
+def apply_penalties(logits, hist, slots, lens, prompt_lens, last, params, vstart: int = 0):
+    """Presence / frequency / repetition penalties over a (vocab-shard of) logits [R, V], out of
+    place (penalties.hip; semantics in ops.reference.apply_penalties). hist [slots, width] int32
+    token histories (width a multiple of 4, below 65536); slots / lens / prompt_lens / last [R]
+    int32; params [R, 4] f32 (`penalty_params`). Stores last[r] to hist[slot, len - 1]. Rows with
+    slot < 0 are copied. The result is a view of an arena buffer: the next call overwrites it.
+    `logits`: a column slice of the padded logits is fine (row stride a multiple of 8)."""
+    if not _gpu(logits):
+        return ref.apply_penalties(logits, hist, slots, lens, prompt_lens, last, params, vstart)
+    R, V = logits.shape
+    stride = (V + 7) // 8 * 8
+    buf = _arena.get(logits.device, "penalties", R * stride, logits.dtype)[:R * stride]
+    if _POISON:
+        _poisoned(buf)
+    out = buf.view(R, stride)[:, :V]
+    torch.ops.bfly.apply_penalties(logits, int(vstart), hist, slots, lens, prompt_lens, last, params, out)
+    return out
+
+
 def topkp_threshold(logits, temps, top_k, top_p, reduce_sum=None, reduce_max=None,
                     use_k: bool = True, use_p: bool = True):
     """Exact per-row top-k / top-p threshold on logit / temperature by radix select (4 passes

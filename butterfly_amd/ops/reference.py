@@ -143,6 +143,49 @@ def logprobs_merge(records):
     return chosen, top_i.to(torch.int32), top_lp
 
 
+def penalty_params(params) -> torch.Tensor:
+    """Host rows [R, 4] f32 (rep, 1 / rep, freq, pres) of `apply_penalties` from (repetition,
+    frequency, presence) triples. 1 / rep is rounded once, in f32, here on the host."""
+    rows = torch.tensor([[float(r), 1.0, float(f), float(p)] for r, f, p in params],
+                        dtype=torch.float32).view(-1, 4)
+    rows[:, 1] = torch.ones((), dtype=torch.float32) / rows[:, 0]
+    return rows
+
+
+def apply_penalties(logits, hist, slots, lens, prompt_lens, last, params, vstart=0):
+    """Presence / frequency / repetition penalties on one vocab shard (penalties.hip), out of
+    place. Row r with slots[r] >= 0 and lens[r] > 0 has the token history hist[slot, :len] with
+    `last[r]` at position len - 1 (stored there as a side effect); positions below
+    prompt_lens[r] are the prompt P, the rest the output O. For the logit x of token t, with c
+    the occurrences of t in O, in f32 and in this order:
+      1. if t in P or c > 0:  x = x * inv_rep if x > 0 else x * rep
+      2. x = x - freq * c
+      3. x = x - pres * (1 if c > 0 else 0)
+    then one rounding to the logits' dtype (bf16 on the GPU). params [R, 4] f32 = (rep, inv_rep,
+    freq, pres) (`penalty_params`). Columns whose token is not in the history, and rows without
+    one, keep their bits. Ids outside [vstart, vstart + V) are other shards' tokens."""
+    R, V = logits.shape
+    out = logits.clone()
+    for r in range(R):
+        slot, n = int(slots[r]), min(int(lens[r]), hist.shape[1])
+        if slot < 0 or slot >= hist.shape[0] or n <= 0:
+            continue
+        hist[slot, n - 1] = last[r]
+        toks = hist[slot, :n].to(torch.int64) - int(vstart)
+        pos = torch.arange(n, device=toks.device)
+        ok = (toks >= 0) & (toks < V)
+        is_out = ok & (pos >= int(prompt_lens[r]))
+        c = torch.bincount(toks[is_out], minlength=V)[:V]
+        seen = torch.bincount(toks[ok], minlength=V)[:V] > 0
+        rep, inv_rep, freq, pres = (params[r, j].to(torch.float32) for j in range(4))
+        x = logits[r].to(torch.float32)
+        y = torch.where(x > 0, x * inv_rep, x * rep)
+        y = y - freq * c.to(torch.float32)
+        y = y - pres * (c > 0).to(torch.float32)
+        out[r] = torch.where(seen, y.to(logits.dtype), logits[r])
+    return out
+
+
 def gather_rows(src, idx, out):
     """out[i] = src[idx[i]] where idx[i] >= 0; other rows of `out` are left as they are."""
     ok = idx >= 0

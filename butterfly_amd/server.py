@@ -17,6 +17,10 @@ Logprobs (`"logprobs": N`, 0..20): the response's choice gains `logprobs` = {"to
 "token_logprobs", "top_logprobs": [[{"token_id", "logprob", "token"}]]} (log_softmax of the raw
 logits; `token` is the decoded piece for text prompts, else null); with streaming each token
 event carries its own entry. Responses to requests without the field are unchanged.
+
+Penalties (`"presence_penalty"`, `"frequency_penalty"` in [-2, 2], `"repetition_penalty"` > 0;
+engine/sampler.py): applied to the logits before sampling, streaming included; a value out of
+range (or not a number) is a 400. Requests without the fields are served exactly as before.
 """
 from __future__ import annotations
 
@@ -165,8 +169,10 @@ def _request_model(BaseModel):
     # built at runtime (pydantic is imported lazily); annotations are real types, not strings
     ns = {"__annotations__": {"model": Optional[str], "prompt": object, "max_tokens": int, "temperature": float,
                               "top_p": float, "top_k": int, "seed": Optional[int], "stop_token_ids": list,
-                              "stream": bool, "logprobs": Optional[int]},
-          "logprobs": None, "model": None, "max_tokens": 16, "temperature": 0.0, "top_p": 1.0, "top_k": 0, "seed": None,
+                              "stream": bool, "logprobs": Optional[int],
+                              # checked by SamplingParams.check_penalties (pydantic would turn a bool into 1.0)
+                              "presence_penalty": object, "frequency_penalty": object, "repetition_penalty": object},
+          "presence_penalty": 0.0, "frequency_penalty": 0.0, "repetition_penalty": 1.0, "logprobs": None, "model": None, "max_tokens": 16, "temperature": 0.0, "top_p": 1.0, "top_k": 0, "seed": None,
           "stop_token_ids": [], "stream": False}
     return type("CompletionRequest", (BaseModel,), ns)
 
@@ -217,7 +223,14 @@ def create_app(loop: ServingLoop):
             raise HTTPException(400, "logprobs must be an integer in 0..20")
         params = SamplingParams(max_tokens=req.max_tokens, temperature=req.temperature, top_p=req.top_p,
                                 top_k=req.top_k, seed=req.seed, stop_token_ids=req.stop_token_ids,
-                                logprobs=req.logprobs)
+                                logprobs=req.logprobs, presence_penalty=req.presence_penalty,
+                                frequency_penalty=req.frequency_penalty, repetition_penalty=req.repetition_penalty)
+        try:
+            params.check_penalties()
+        except ValueError as e:
+            raise HTTPException(400, str(e))
+        if params.needs_penalty and loop.llm.plan.mesh.pp > 1:
+            raise HTTPException(400, "penalties are not supported with pipeline parallelism (pp > 1)")
         if req.stream:
             gid = loop.submit(ids, params, stream=True)
 

@@ -321,6 +321,35 @@ void logprobs_merge(const Tensor& records, Tensor& chosen_lp, Tensor& top_ids, T
                               top_ids.data_ptr<int>(), top_lp.data_ptr<float>(), cur_stream());
 }
 
+// Presence / frequency / repetition penalties (penalties.hip): out [rows, V] bf16 = penalised logits.
+void apply_penalties(const Tensor& logits, int64_t vstart, Tensor& hist, const Tensor& slots, const Tensor& lens,
+                     const Tensor& prompt_lens, const Tensor& last, const Tensor& params, Tensor& out) {
+  CHECK_GPU(logits); CHECK_BF16(logits); CHECK_GPU(out); CHECK_BF16(out); CHECK_GPU(hist); CHECK_I32(hist);
+  CHECK_GPU(slots); CHECK_I32(slots); CHECK_GPU(lens); CHECK_I32(lens); CHECK_GPU(prompt_lens); CHECK_I32(prompt_lens);
+  CHECK_GPU(last); CHECK_I32(last); CHECK_GPU(params);
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && logits.stride(0) % 8 == 0, "apply_penalties: logits");
+  CHECK_ALIGN16(logits);
+  const int64_t rows = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(vstart >= 0 && vstart + V < (1ll << 24), "apply_penalties: token ids must stay below 2^24");
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == rows && out.size(1) == V && out.stride(1) == 1 &&
+                  out.stride(0) % 8 == 0, "apply_penalties: out [rows, V] bf16, row stride a multiple of 8");
+  CHECK_ALIGN16(out);
+  TORCH_CHECK(hist.dim() == 2 && hist.is_contiguous() && hist.size(1) % 4 == 0 && hist.size(1) < 65536 &&
+                  hist.size(0) < (1ll << 31), "apply_penalties: hist [slots, width] int32, width % 4 == 0 and < 65536");
+  CHECK_ALIGN16(hist);
+  TORCH_CHECK(slots.is_contiguous() && slots.numel() == rows && lens.is_contiguous() && lens.numel() == rows &&
+                  prompt_lens.is_contiguous() && prompt_lens.numel() == rows && last.is_contiguous() &&
+                  last.numel() == rows, "apply_penalties: slots / lens / prompt_lens / last [rows] int32");
+  TORCH_CHECK(params.scalar_type() == at::kFloat && params.is_contiguous() && params.dim() == 2 &&
+                  params.size(0) == rows && params.size(1) == 4, "apply_penalties: params [rows, 4] f32");
+  CHECK_ALIGN16(params);
+  c10::DeviceGuard g(logits.device());
+  bfly::launch_apply_penalties(bf(logits), logits.stride(0), rows, V, vstart, hist.data_ptr<int>(), hist.size(1),
+                               hist.size(0), slots.data_ptr<int>(), lens.data_ptr<int>(),
+                               prompt_lens.data_ptr<int>(), last.data_ptr<int>(), params.data_ptr<float>(),
+                               reinterpret_cast<bfly::bf16*>(out.data_ptr()), out.stride(0), cur_stream());
+}
+
 // Exact top-k / top-p radix select (sample.hip). `ws` is one zeroed f32 buffer holding
 // state [rows, 8] | smax [rows] (int32 bits) | hist [rows, 512].
 struct TkpViews { float* state; int* smax; float* hist; };
@@ -1312,6 +1341,8 @@ TORCH_LIBRARY(bfly, m) {
   m.def("logprobs_partial(Tensor logits, Tensor ids, int n, int vstart, Tensor(a!) record, "
         "Tensor(b!) workspace) -> ()");
   m.def("logprobs_merge(Tensor records, Tensor(a!) chosen_lp, Tensor(b!) top_ids, Tensor(c!) top_lp) -> ()");
+  m.def("apply_penalties(Tensor logits, int vstart, Tensor(a!) hist, Tensor slots, Tensor lens, Tensor prompt_lens, "
+        "Tensor last, Tensor params, Tensor(b!) out) -> ()");
   m.def("tkp_begin(Tensor logits, Tensor temps, Tensor top_k, Tensor top_p, Tensor(a!) ws) -> ()");
   m.def("tkp_pass(Tensor logits, Tensor temps, Tensor(a!) ws, int pass_, int phase) -> ()");
   m.def("tkp_select(Tensor top_p, Tensor(a!) ws, int rows, int pass_, int phase) -> ()");
@@ -1411,6 +1442,7 @@ TORCH_LIBRARY_IMPL(bfly, CUDA, m) {
   m.impl("sample", &sample);
   m.impl("logprobs_partial", &logprobs_partial);
   m.impl("logprobs_merge", &logprobs_merge);
+  m.impl("apply_penalties", &apply_penalties);
   m.impl("tkp_begin", &tkp_begin);
   m.impl("tkp_pass", &tkp_pass);
   m.impl("tkp_select", &tkp_select);

@@ -139,6 +139,18 @@ void launch_logprobs_partial(const bf16* logits, long row_stride, int rows, int 
 void launch_logprobs_merge(const float* records, int tp, int rows, int n, float* chosen_lp,
                            int* top_ids, float* top_lp, hipStream_t stream);
 
+// penalties.hip: presence / frequency / repetition penalties, out of place. hist
+// [hist_rows][hist_stride] int32 token histories (hist_stride % 4 == 0); per row: slots (< 0: the
+// row is copied bit for bit), lens (tokens so far, the newest one being last[row], which is
+// also stored to hist[slot][len - 1]), prompt_lens (positions below it are prompt tokens),
+// params [rows][4] f32 (rep, 1 / rep, freq, pres). Row strides in elements.
+constexpr int kPenaltyChunk = 4096;
+inline int penalty_chunks(int V) { return (V + kPenaltyChunk - 1) / kPenaltyChunk; }
+void launch_apply_penalties(const bf16* logits, long row_stride, int rows, int V, int vstart,
+                            int* hist, long hist_stride, int hist_rows, const int* slots,
+                            const int* lens, const int* prompt_lens, const int* last,
+                            const float* params, bf16* out, long out_stride, hipStream_t stream);
+
 // gemm.hip
 GemmPlan plan_gemm(int M, int N, int K);
 size_t gemm_workspace_bytes(int M, int N, int K);
