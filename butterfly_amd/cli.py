@@ -18,6 +18,8 @@ import os
 import subprocess
 import sys
 
+from .config import WEIGHT_DTYPES   # standard library only, like this module's other imports
+
 
 def _strategy(s: str | None):
     if not s or s == "auto":
@@ -174,7 +176,8 @@ def cmd_info(a) -> int:
     from .utils import flags
 
     info = {"torch": torch.__version__, "hip": torch.version.hip, "gpu": torch.cuda.is_available(),
-            "kernels_loaded": ops.load_library(), "kernel_lib": ops.library_path(), "flags": flags.dump()}
+            "kernels_loaded": ops.load_library(), "kernel_lib": ops.library_path(), "weight_dtypes": list(WEIGHT_DTYPES),
+            "flags": flags.dump()}
     if torch.cuda.is_available():
         p = torch.cuda.get_device_properties(0)
         info["device"] = {"name": p.name, "arch": getattr(p, "gcnArchName", ""), "memory_gb": p.total_memory / 1e9,
@@ -216,8 +219,9 @@ def main(argv=None) -> int:
                    help="subtracted from a token's logit per occurrence among the generated tokens (-2..2)")
     g.add_argument("--repetition-penalty", type=float, default=1.0,
                    help="divides the positive (multiplies the negative) logits of prompt and generated tokens (> 0)")
-    g.add_argument("--weight-dtype", default="auto", choices=["auto", "bf16", "fp8"],
-                   help="dense projection weights: bf16, or fp8 (weight-only e4m3); auto = BFLY_WEIGHT_DTYPE")
+    g.add_argument("--weight-dtype", default="auto", choices=["auto", *WEIGHT_DTYPES],
+                   help="dense projection weights: bf16, fp8 (weight-only e4m3) or mxfp4 (weight-only OCP MXFP4); "
+                        "auto = BFLY_WEIGHT_DTYPE")
     g.add_argument("--snapshot-dir", default=None,
                    help="write request-state snapshots here; a restarted job (launch --max-restarts) resumes from them")
     g.add_argument("--snapshot-every", type=int, default=4, help="engine steps between snapshots")
@@ -230,8 +234,9 @@ def main(argv=None) -> int:
     s.add_argument("--port", type=int, default=8000)
     s.add_argument("--max-batch", type=int, default=64)
     s.add_argument("--max-seq-len", type=int, default=4096)
-    s.add_argument("--weight-dtype", default="auto", choices=["auto", "bf16", "fp8"],
-                   help="dense projection weights: bf16, or fp8 (weight-only e4m3); auto = BFLY_WEIGHT_DTYPE")
+    s.add_argument("--weight-dtype", default="auto", choices=["auto", *WEIGHT_DTYPES],
+                   help="dense projection weights: bf16, fp8 (weight-only e4m3) or mxfp4 (weight-only OCP MXFP4); "
+                        "auto = BFLY_WEIGHT_DTYPE")
     s.set_defaults(fn=cmd_serve)
     b = sub.add_parser("bench", add_help=False)
     b.add_argument("rest", nargs=argparse.REMAINDER)

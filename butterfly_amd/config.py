@@ -194,6 +194,11 @@ class ParallelConfig:
         return cls(**{k: v for k, v in d.items() if k in names})
 
 
+# element types of the dense projection weights an engine can hold (EngineConfig.weight_dtype,
+# --weight-dtype, BFLY_WEIGHT_DTYPE, `info`): engine.weight_dtype() resolves a name to one of them
+WEIGHT_DTYPES = ("bf16", "fp8", "mxfp4")
+
+
 @dataclass
 class EngineConfig:
     max_batch: int = 64               # max concurrent sequences per DP replica
@@ -220,8 +225,10 @@ class EngineConfig:
     # element type of the dense projection weights (QKV, O, gate/up, down): "bf16", or "fp8"
     # (weight-only e4m3 codes with one f32 scale per output row, quantised by the engine once the
     # weights are final: half the weight bytes streamed per decode step, the freed HBM goes to
-    # KV pages; activations and accumulation stay as they are). "auto": the BFLY_WEIGHT_DTYPE flag.
-    weight_dtype: str = "auto"
+    # KV pages; activations and accumulation stay as they are), or "mxfp4" (weight-only OCP MXFP4:
+    # e2m1 codes with one e8m0 scale per 32 elements along K, 4.25 bits per weight). "auto": the
+    # BFLY_WEIGHT_DTYPE flag.
+    weight_dtype: str = "auto"          # "auto" or one of WEIGHT_DTYPES
     # context-parallel prefill across data-parallel replicas (pp == 1, no EP): a prompt of at
     # least this many tokens is prefilled by ALL dp replicas together (ring or Ulysses
     # attention, parallel/context_parallel.py), its K/V collected in the cache of the replica

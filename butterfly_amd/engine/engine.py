@@ -33,7 +33,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..config import EngineConfig, ModelConfig
+from ..config import WEIGHT_DTYPES, EngineConfig, ModelConfig
 from ..models import Shard, build_model
 from ..parallel.comm import Communicator, NativeWork
 from ..parallel.mesh import Mesh
@@ -146,7 +146,7 @@ class LLMEngine:
             self.model.quantize_weights(self.weight_dtype)
             if self.device.type == "cuda":
                 ops.reserve_w8_workspace(self.device, max(engine_cfg.max_prefill_tokens, engine_cfg.max_batch),
-                                         self.model.w8_shapes())
+                                         self.model.w8_shapes(), self.weight_dtype)
                 torch.cuda.empty_cache()
         elif getattr(self.model, "weight_dtype", "bf16") != "bf16":
             self.weight_dtype = self.model.weight_dtype      # handed an already quantised model
@@ -231,7 +231,8 @@ class LLMEngine:
                                   max_batch=max(engine_cfg.graph_batch_sizes + [engine_cfg.max_batch]),
                                   max_ctx=engine_cfg.max_seq_len, num_kv_heads=d.hkv, head_dim=cfg.head_dim,
                                   shapes=self.model.gemm_shapes(), w8_shapes=self.model.w8_shapes(),
-                                  vocab=min(d.vocab, max(0, cfg.vocab_size - d.vocab0)))
+                                  vocab=min(d.vocab, max(0, cfg.vocab_size - d.vocab0)),
+                                  weight_dtype=self.weight_dtype)
         buckets = [b for b in engine_cfg.graph_batch_sizes if b <= engine_cfg.max_batch] or [engine_cfg.max_batch]
         if self.async_pp and self.scheduler.group_batch not in buckets:
             buckets.append(self.scheduler.group_batch)    # a full group replays one graph
@@ -1191,16 +1192,18 @@ class LLMEngine:
         return [self.requests[r].output for r in rids]
 
 
+_WEIGHT_DTYPE_ALIASES = {"bfloat16": "bf16", "fp8_e4m3": "fp8", "e4m3": "fp8", "mxfp4_e2m1": "mxfp4"}
+
+
 def weight_dtype(name: str) -> str:
-    """EngineConfig.weight_dtype -> "bf16" | "fp8" ("auto": the BFLY_WEIGHT_DTYPE flag)."""
+    """EngineConfig.weight_dtype -> one of config.WEIGHT_DTYPES ("auto": the BFLY_WEIGHT_DTYPE flag)."""
     if name in (None, "auto"):
         name = flags.get("BFLY_WEIGHT_DTYPE")
     name = str(name).strip().lower()
-    if name in ("bf16", "bfloat16"):
-        return "bf16"
-    if name in ("fp8", "fp8_e4m3", "e4m3"):
-        return "fp8"
-    raise ValueError(f"unknown weight_dtype {name!r} (auto | bf16 | fp8)")
+    name = _WEIGHT_DTYPE_ALIASES.get(name, name)
+    if name in WEIGHT_DTYPES:
+        return name
+    raise ValueError(f"unknown weight_dtype {name!r} (auto | {' | '.join(WEIGHT_DTYPES)})")
 
 
 def kv_cache_dtype(name: str, model_dtype: torch.dtype) -> torch.dtype:

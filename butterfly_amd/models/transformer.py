@@ -218,49 +218,66 @@ class TransformerLM:
     _W8_KINDS = ("qkv_w", "o_w", "gu_w", "down_w")
 
     def quantize_weights(self, weight_dtype: str = "fp8") -> int:
-        """Replace the four dense projections of every local layer by FP8 e4m3 codes with one
-        f32 scale per (local shard) output row (ops.quantize_fp8), one tensor at a time so the
-        peak stays at the bf16 model's. Embedding, LM head and norms keep the model dtype. The
-        scales are per local row: a row-parallel shard (O, down) scales its own partial sum
-        before the all-reduce, so the quantised values depend on the TP split. Quantised
-        projections return plain tensors: the split-K / row-scale consumer fusions of the bf16
-        plans and the packed decode copies are off. Call after the weights are final (random
-        init or checkpoint load). Returns the bytes freed."""
+        """Replace the four dense projections of every local layer by weight-only codes, one
+        tensor at a time so the peak stays at the bf16 model's. Embedding, LM head and norms
+        keep the model dtype.
+          "fp8":   e4m3 codes with one f32 scale per (local shard) output row (ops.quantize_fp8).
+                   The scales are per local row: a row-parallel shard (O, down) scales its own
+                   partial sum before the all-reduce, so the quantised values depend on the TP
+                   split.
+          "mxfp4": OCP MXFP4 (ops.quantize_mxfp4): p[name] becomes the uint8 codes [N, K / 2],
+                   wscale[name] the e8m0 bytes [N, K / 32]. Scale blocks lie along K and a local
+                   K is a multiple of 32, so no shard splits a block: every TP split holds the
+                   same dequantised weights.
+        Quantised projections return plain tensors: the split-K / row-scale consumer fusions of
+        the bf16 plans and the packed decode copies are off. Call after the weights are final
+        (random init or checkpoint load). Returns the bytes freed."""
         if weight_dtype in ("bf16", None):
             return 0
-        if weight_dtype != "fp8":
-            raise ValueError(f"quantize_weights: unknown weight dtype {weight_dtype!r} (fp8)")
+        if weight_dtype not in ("fp8", "mxfp4"):
+            raise ValueError(f"quantize_weights: unknown weight dtype {weight_dtype!r} (fp8 | mxfp4)")
+        what = "FP8" if weight_dtype == "fp8" else "MXFP4"
         c = self.cfg
         if c.is_moe:
-            raise ValueError("FP8 weights: MoE models are not supported (no FP8 grouped expert GEMM)")
+            raise ValueError(f"{what} weights: MoE models are not supported (no {what} grouped expert GEMM)")
         if c.bias:
-            raise ValueError("FP8 weights: models with linear biases are not supported (the FP8 GEMM has no bias epilogue)")
+            raise ValueError(f"{what} weights: models with linear biases are not supported (the {what} GEMM has no "
+                             "bias epilogue)")
         if c.act != "silu":
-            raise ValueError("FP8 weights: only SwiGLU models are supported (the FP8 GEMM has no GELU FFN path)")
+            raise ValueError(f"{what} weights: only SwiGLU models are supported (the {what} GEMM has no GELU FFN path)")
         if self.wscale:
+            if self.weight_dtype != weight_dtype:
+                raise ValueError(f"{what} weights: the model already holds {self.weight_dtype} weights")
             return 0
         if self.packed:
-            raise ValueError("FP8 weights: quantise before pack_decode_weights")
+            raise ValueError(f"{what} weights: quantise before pack_decode_weights")
+        names = [f"l{i}.{kind}" for i in self.layer_ids for kind in self._W8_KINDS]
+        if weight_dtype == "mxfp4":
+            for name in names:
+                if self.p[name].shape[1] % 32 != 0:
+                    raise ValueError(f"MXFP4 weights: {name} has a local K of {self.p[name].shape[1]}, not a "
+                                     "multiple of the 32-element scale block")
+        quantise = ops.quantize_fp8 if weight_dtype == "fp8" else ops.quantize_mxfp4
         before = self.local_bytes()
-        for i in self.layer_ids:
-            for kind in self._W8_KINDS:
-                name = f"l{i}.{kind}"
-                code, scale = ops.quantize_fp8(self.p[name])
-                self.p[name] = code
-                self.wscale[name] = scale
-        self.weight_dtype = "fp8"
+        for name in names:
+            code, scale = quantise(self.p[name])
+            self.p[name] = code
+            self.wscale[name] = scale
+        self.weight_dtype = weight_dtype
         self.defer_qkv = self.defer_reduce = False
         self.rowscale_rows = 0
         return before - self.local_bytes()
 
     def w8_shapes(self) -> list:
-        """(N, K) of the FP8-quantised projections (ops.reserve_workspace)."""
-        return sorted({tuple(self.p[k].shape) for k in self.wscale})
+        """Logical (N, K) of the quantised projections (ops.reserve_workspace); MXFP4 codes
+        hold two elements per byte."""
+        per_byte = 2 if self.weight_dtype == "mxfp4" else 1
+        return sorted({(self.p[k].shape[0], self.p[k].shape[1] * per_byte) for k in self.wscale})
 
     def logical_params(self) -> list[LogicalParam]:
         """Every logical (HF-style) parameter slice this rank holds."""
         if self.wscale:
-            raise RuntimeError("logical_params: the model holds FP8-quantised weights; checkpoints are saved "
+            raise RuntimeError(f"logical_params: the model holds {self.weight_dtype}-quantised weights; checkpoints are saved "
                                "from / loaded into an unquantised model (quantise after loading)")
         c, d, s = self.cfg, self.dims, self.shard
         h, D = c.hidden_size, c.head_dim
@@ -466,11 +483,12 @@ class TransformerLM:
         return delta, partial
 
     def _proj(self, name: str, x, epilogue: str = "none", bias=None, defer: bool = False):
-        """One of the four dense projections (qkv / o / gate-up / down) of a layer: the FP8
-        GEMM on its codes and row scales when the weight is quantised (plain bf16 output, no
+        """One of the four dense projections (qkv / o / gate-up / down) of a layer: the FP8 or
+        MXFP4 GEMM on its codes and scales when the weight is quantised (plain bf16 output, no
         bias), else ops.linear on the bf16 weight and its packed copy."""
         if name in self.wscale:
-            return ops.linear_w8(x, self.p[name], self.wscale[name], epilogue=epilogue)
+            linear_q = ops.linear_w4 if self.weight_dtype == "mxfp4" else ops.linear_w8
+            return linear_q(x, self.p[name], self.wscale[name], epilogue=epilogue)
         return ops.linear(x, self.p[name], bias=bias, epilogue=epilogue, defer=defer,
                           packed=self.packed.get(name))
 
@@ -752,8 +770,10 @@ class TransformerLM:
         return 2 * len(self.layer_ids) * self.dims.hkv * self.cfg.head_dim * bits // 8
 
     def gemm_shapes(self) -> list:
-        """(N, K) of every weight this stage multiplies by (workspace sizing)."""
-        return sorted({tuple(w.shape) for k, w in self.p.items() if w.dim() == 2 and k != "embed"})
+        """Logical (N, K) of every weight this stage multiplies by (workspace sizing)."""
+        per_byte = 2 if self.weight_dtype == "mxfp4" else 1
+        return sorted({(w.shape[0], w.shape[1] * (per_byte if k in self.wscale else 1))
+                       for k, w in self.p.items() if w.dim() == 2 and k != "embed"})
 
     def allocate_kv_cache(self, num_blocks: int, block_size: int, dtype: Optional[torch.dtype] = None) -> list:
         D, hk = self.cfg.head_dim, self.dims.hkv

@@ -149,6 +149,8 @@ def set_poison(on: bool) -> None:
 
 
 def _poisoned(t: torch.Tensor) -> torch.Tensor:
+    if t.dtype == torch.uint8:      # MXFP4 codes / scales: the sentinel must fit a byte
+        return t.fill_(0xA5)
     return t.fill_(float("nan") if t.is_floating_point() else -7777777)
 
 
@@ -171,13 +173,17 @@ def arena_scope(name) -> None:
     _scope.name = name
 
 
-def reserve_w8_workspace(device, max_tokens: int, w8_shapes) -> None:
-    """The FP8 weight-only GEMM's buffers for quantised projections of shapes `w8_shapes`
+def reserve_w8_workspace(device, max_tokens: int, w8_shapes, weight_dtype: str = "fp8") -> None:
+    """The weight-only GEMM's buffers for quantised projections of logical shapes `w8_shapes`
     (N, K) at up to `max_tokens` rows: the native kernel's split-K slabs and, when some row
-    count or shape takes the dequantise route, a bf16 scratch of the largest projection and of
-    the largest unscaled GEMM result (SwiGLU projections)."""
+    count or shape takes the dequantise route, a bf16 scratch of the largest projection and
+    (FP8 only) of the largest unscaled GEMM result (SwiGLU projections). `weight_dtype`: "fp8"
+    or "mxfp4"; the MXFP4 scratch holds the final weights, so it needs no second buffer."""
     if not load_library():
         return
+    L = torch.ops.bfly
+    check, size, slot = ((L.gemm_w4_check, L.gemm_w4_workspace_size, "gemm_w4") if weight_dtype == "mxfp4"
+                         else (L.gemm_w8_check, L.gemm_w8_workspace_size, "gemm_w8"))
     w8 = {(int(n), int(k)) for n, k in w8_shapes}
     if w8:
         slab, deq, tmp = 0, 0, 0
@@ -185,31 +191,33 @@ def reserve_w8_workspace(device, max_tokens: int, w8_shapes) -> None:
             if m > max_tokens:
                 continue
             for n, k in w8:
-                if any(torch.ops.bfly.gemm_w8_check(m, n, k, e) != 0 for e in (0, 2)):
+                if any(check(m, n, k, e) != 0 for e in (0, 2)):
                     deq = max(deq, n * k)
                     tmp = max(tmp, m * n)
                 else:
-                    slab = max(slab, torch.ops.bfly.gemm_w8_workspace_size(m, n, k))
+                    slab = max(slab, size(m, n, k))
         if slab:
-            _arena.get(device, "gemm_w8", slab // 4 + 1, torch.float32)
+            _arena.get(device, slot, slab // 4 + 1, torch.float32)
         if deq:
             _arena.get(device, "w8_deq", deq, torch.bfloat16)
-            _arena.get(device, "w8_tmp", tmp, torch.bfloat16)
+            if weight_dtype != "mxfp4":
+                _arena.get(device, "w8_tmp", tmp, torch.bfloat16)
 
 
 def reserve_workspace(device, max_tokens: int, max_n: int, max_k: int, max_batch: int = 0,
                       max_ctx: int = 0, num_kv_heads: int = 0, head_dim: int = 128, shapes=(),
-                      w8_shapes=(), vocab: int = 0) -> None:
+                      w8_shapes=(), vocab: int = 0, weight_dtype: str = "fp8") -> None:
     """Pre-size every workspace for problems up to the given bounds (call before capture).
     `shapes`: the model's GEMM weight shapes (N, K); the split-K slab need is the max over them
     and every token-count bucket of the plan table (a tuned plan may split a small projection
-    more than the largest one is split). `w8_shapes`: the (N, K) of FP8-quantised projections:
-    sizes the native FP8 GEMM's split-K slabs and, for token counts (or shapes) that take the
-    dequantise route, the bf16 scratch of the largest of them. `vocab`: columns of the logits
+    more than the largest one is split). `w8_shapes`: the logical (N, K) of the projections
+    quantised to `weight_dtype` ("fp8" | "mxfp4"): sizes the native weight-only GEMM's split-K
+    slabs and, for token counts (or shapes) that take the dequantise route, the bf16 scratch of
+    the largest of them. `vocab`: columns of the logits
     shard; sizes the logprobs partials for `max_batch` rows with the most alternatives."""
     if not load_library():
         return
-    reserve_w8_workspace(device, max_tokens, w8_shapes)
+    reserve_w8_workspace(device, max_tokens, w8_shapes, weight_dtype)
     ws = 0
     nk = {(int(max_n), int(max_k))} | {(int(n), int(k)) for n, k in shapes}
     for m in sorted({1, 16, 32, 48, 64, 128, 256, 512, max_tokens}):
@@ -698,6 +706,63 @@ def linear_w8(x, code, scale, epilogue: str = "none", out=None):
     if M:
         torch.ops.bfly.w8_scale_cols(y, scale, out, epi)
     return out
+
+
+def quantize_mxfp4(w):
+    """OCP MXFP4 weight-only quantisation of a [N, K] weight, K % 32 == 0
+    (ops.reference.quantize_mxfp4 has the format): returns (code uint8 [N, K / 2], two e2m1
+    codes per byte, scale uint8 [N, K / 32], one e8m0 byte per 32 elements)."""
+    if not _gpu(w):
+        return ref.quantize_mxfp4(w)
+    if w.dim() != 2 or w.dtype != torch.bfloat16 or w.shape[1] % ref.MXFP4_BLOCK != 0:
+        raise ValueError("quantize_mxfp4: a 2-D bf16 weight with K % 32 == 0")
+    if w.stride(1) != 1 or w.stride(0) % 8 != 0 or w.data_ptr() % 16 != 0:
+        w = w.contiguous()
+    N, K = w.shape
+    code = _empty(N, K // 2, dtype=torch.uint8, device=w.device)
+    scale = _empty(N, K // ref.MXFP4_BLOCK, dtype=torch.uint8, device=w.device)
+    torch.ops.bfly.quant_mxfp4(w, code, scale)
+    return code, scale
+
+
+def dequantize_mxfp4(code, scale, dtype=None, out=None):
+    """dtype(value(code) * 2^(scale - 127)) [N, K], exact (GPU: bf16, dequant_mxfp4_kernel).
+    Scale bytes must lie in 2 .. 252, the range `quantize_mxfp4` writes (every result a normal
+    bf16); other bytes are invalid input: the GPU kernels give 0 for byte 0 and infinity for 255."""
+    if not _gpu(code):
+        y = ref.dequantize_mxfp4(code, scale, dtype or torch.float32)
+        return y if out is None else out.copy_(y)
+    if dtype not in (None, torch.bfloat16):
+        raise ValueError("dequantize_mxfp4: the GPU kernel writes bf16")
+    if out is None:
+        out = _empty(code.shape[0], 2 * code.shape[1], dtype=torch.bfloat16, device=code.device)
+    torch.ops.bfly.dequant_mxfp4(code, scale, out)
+    return out
+
+
+def linear_w4(x, code, scale, epilogue: str = "none", out=None):
+    """y = linear(x, dequantize_mxfp4(code, scale), epilogue): the MXFP4 weight-only
+    counterpart of `linear` (no bias). Shapes and row counts the native kernel takes
+    (gemm_w4_check) stream the codes once (gemm_w4.hip gemm_w4_kernel); every other one writes
+    the dequantised weights, which bf16 holds exactly, into the arena's scratch and runs
+    `linear` on them with the same epilogue. Scale bytes must lie in 2 .. 252 (`dequantize_mxfp4`)."""
+    if not _gpu(x):
+        return ref.linear_w4(x, code, scale, epilogue, out)
+    if epilogue not in ("none", "silu"):
+        raise ValueError(f"linear_w4: epilogue {epilogue!r} not supported (no bias)")
+    M, K = x.shape
+    N = code.shape[0]
+    epi = EPILOGUES[epilogue]
+    if out is None:
+        out = _empty(M, N // 2 if epilogue == "silu" else N, dtype=x.dtype, device=x.device)
+    if torch.ops.bfly.gemm_w4_check(M, N, K, epi) == 0:
+        need = torch.ops.bfly.gemm_w4_workspace_size(M, N, K)
+        ws = _arena.get(x.device, "gemm_w4", need // 4 + 1, torch.float32) if need else None
+        torch.ops.bfly.gemm_w4(x, code, scale, out, epi, ws, False)
+        return out
+    wd = _arena.get(x.device, "w8_deq", N * K, torch.bfloat16)[:N * K].view(N, K)
+    torch.ops.bfly.dequant_mxfp4(code, scale, wd)
+    return linear(x, wd, epilogue=epilogue, out=out)
 
 
 def linear_silu_gate(x, w, gates, e0: int, num_local: int, packed=None):

@@ -466,6 +466,52 @@ def linear_w8(x, code, scale, epilogue="none", out=None):
     return out
 
 
+MXFP4_BLOCK = 32                                       # elements per e8m0 scale
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)  # magnitude of code & 7; bit 3 is the sign
+
+
+def quantize_mxfp4(w):
+    """OCP MXFP4 weight-only quantisation of a [N, K] weight, K % 32 == 0: per row and block of
+    32 elements along K, E = clamp(floor(log2(amax)) - 2, -125, 125) (0 for an all-zero block),
+    scale = uint8(E + 127) (e8m0), code = RNE_e2m1(w / 2^E) saturating at +-6 (ties to the code
+    with an even low bit, bit 3 the sign). Returns (code uint8 [N, K / 2], element 2 i in the
+    low nibble of byte i (the torch.float4_e2m1fn_x2 convention), scale uint8 [N, K / 32]).
+    Every step is exact: the exponent is read with frexp, 2^E is built with ldexp."""
+    if w.dim() != 2 or w.shape[1] % MXFP4_BLOCK != 0:
+        raise ValueError(f"quantize_mxfp4: a [N, K] weight with K % {MXFP4_BLOCK} == 0, got {tuple(w.shape)}")
+    N, K = w.shape
+    wf = w.float().view(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = wf.abs().amax(dim=2)
+    _, ex = torch.frexp(amax)                          # amax = m * 2^ex, .5 <= m < 1: floor(log2) = ex - 1
+    E = (ex.to(torch.int32) - 3).clamp_(-125, 125)
+    E = torch.where(amax > 0, E, torch.zeros_like(E))
+    t = torch.ldexp(wf.abs(), -E[:, :, None])          # |w| / 2^E, below 8
+    v = torch.where(t < 2, torch.round(t * 2) / 2, torch.where(t < 4, torch.round(t), torch.round(t / 2) * 2))
+    v = v.clamp_(max=6.0)                              # torch.round: halves to even, i.e. to the even code
+    mag = torch.where(v < 2, v * 2, torch.where(v < 4, v + 2, v / 2 + 4)).to(torch.uint8)
+    c = (mag | (torch.signbit(wf).to(torch.uint8) << 3)).view(N, K // 2, 2)
+    return c[:, :, 0] | (c[:, :, 1] << 4), (E + 127).to(torch.uint8)
+
+
+def dequantize_mxfp4(code, scale, dtype=torch.float32):
+    """dtype(value(code) * 2^(scale - 127)) [N, K] of codes [N, K / 2] and scales [N, K / 32];
+    exact in bf16 and wider for scale bytes 2 .. 252, the range quantize_mxfp4 writes; other scale
+    bytes are invalid input (the GPU kernels do not reproduce this function on them)."""
+    N, Kb = code.shape
+    c = torch.stack((code & 15, code >> 4), dim=2).view(N, 2 * Kb).long()
+    lut = torch.tensor(E2M1_VALUES + tuple(-x for x in E2M1_VALUES), dtype=torch.float32, device=code.device)
+    e = (scale.to(torch.int32) - 127).repeat_interleave(MXFP4_BLOCK, dim=1)
+    return torch.ldexp(lut[c], e).to(dtype)
+
+
+def linear_w4(x, code, scale, epilogue="none", out=None):
+    """linear(x, dequantize_mxfp4(code, scale), epilogue): f32 accumulation over the exact
+    dequantised weights, the optional SwiGLU epilogue, one rounding to x.dtype. No bias."""
+    if epilogue not in ("none", "silu"):
+        raise ValueError(f"linear_w4: epilogue {epilogue!r} not supported (no bias)")
+    return linear(x, dequantize_mxfp4(code, scale, torch.float32), None, epilogue, out)
+
+
 def attn_prefill(q, k, v, cu_seqlens, max_seqlen, scale, causal=True, out=None, cu_seqlens_k=None,
                  return_lse=False):
     """q [T, Hq, D], k/v [Tk, Hkv, D]; varlen sequences given by cu_seqlens (int32), keys by

@@ -36,6 +36,7 @@ template <> struct DType<float> { static constexpr at::ScalarType v = at::kFloat
 template <> struct DType<int> { static constexpr at::ScalarType v = at::kInt; };
 template <> struct DType<long> { static constexpr at::ScalarType v = at::kLong; };
 template <> struct DType<uint64_t> { static constexpr at::ScalarType v = at::kLong; };   // bit patterns in int64 storage
+template <> struct DType<uint8_t> { static constexpr at::ScalarType v = at::kByte; };   // MXFP4 codes and scales
 
 // extra conditions of an accessor (`need`)
 enum : unsigned { kAlign16 = 1, kAlign8 = 2, kLd8 = 4, kLd4 = 8 };   // base address; leading dimension % n
@@ -727,6 +728,49 @@ void gemm_w8(const Tensor& x, const Tensor& code, const Tensor& scale, Tensor& o
               " (rc=", rc, ")");
 }
 
+// OCP MXFP4 weight-only linear layers (gemm_w4.hip): uint8 codes [N, K / 2] (two e2m1 codes per
+// byte), uint8 e8m0 scales [N, K / 32].
+void quant_mxfp4(const Tensor& w, Tensor& code, Tensor& scale) {
+  const Op op("quant_mxfp4", w, "w");
+  const Rows<bf16> wr = op.rows<bf16>(w, "w", {-1, -1}, kAlign16 | kLd8);
+  const int64_t N = w.size(0), K = w.size(1);
+  TORCH_CHECK(K % 32 == 0 && K < (1LL << 31) && N < (1LL << 31), "quant_mxfp4: K % 32, shape");
+  uint8_t* cp = op.shaped<uint8_t>(code, "code", {N, K / 2}, kAlign16);
+  uint8_t* sp = op.shaped<uint8_t>(scale, "scale", {N, K / 32});
+  auto g = op.guard();
+  bfly::launch_quant_mxfp4(wr.p, wr.ld, N, (int)K, cp, sp, cur_stream());
+}
+
+void dequant_mxfp4(const Tensor& code, const Tensor& scale, Tensor& out) {
+  const Op op("dequant_mxfp4", code, "code");
+  const uint8_t* cp = op.shaped<uint8_t>(code, "code", {-1, -1}, kAlign16);
+  const int64_t N = code.size(0), K = 2 * code.size(1);
+  TORCH_CHECK(K % 32 == 0 && K < (1LL << 31), "dequant_mxfp4: K % 32, shape");
+  const uint8_t* sp = op.shaped<uint8_t>(scale, "scale", {N, K / 32});
+  const Rows<bf16> o = op.rows<bf16>(out, "out", {N, K}, kAlign16 | kLd8);
+  auto g = op.guard();
+  bfly::launch_dequant_mxfp4(cp, sp, N, (int)K, o.p, o.ld, cur_stream());
+}
+
+void gemm_w4(const Tensor& x, const Tensor& code, const Tensor& scale, Tensor& out, int64_t epilogue,
+             const OptTensor& workspace, bool any_m, int64_t force_sk) {
+  const Op op("gemm_w4", x, "x");
+  TORCH_CHECK(epilogue == bfly::EPI_NONE || epilogue == bfly::EPI_SILU, "gemm_w4: epilogue none / silu");
+  const Rows<bf16> xr = op.rows<bf16>(x, "x", {-1, -1}, kAlign16 | kLd8);
+  const int M = x.size(0), K = x.size(1);
+  TORCH_CHECK(K % 32 == 0, "gemm_w4: K % 32");
+  const uint8_t* cp = op.shaped<uint8_t>(code, "code", {-1, K / 2}, kAlign16);
+  const int N = code.size(0);
+  const uint8_t* sp = op.shaped<uint8_t>(scale, "scale", {N, K / 32}, kAlign16);
+  const Rows<bf16> o = op.rows<bf16>(out, "out", {M, epilogue == bfly::EPI_SILU ? N / 2 : N}, kAlign8 | kLd4);
+  const Workspace ws = workspace_of(op, workspace, kAlign16);
+  auto g = op.guard();
+  const int rc = bfly::launch_gemm_w4(xr.p, xr.ld, cp, sp, M, N, K, (int)epilogue, o.p, o.ld, ws.p, ws.bytes,
+                                      cur_stream(), any_m, (int)force_sk);
+  TORCH_CHECK(rc == 0, "gemm_w4: shape / plan not taken by the native kernel M=", M, " N=", N, " K=", K,
+              " (rc=", rc, ")");
+}
+
 // 0 when the plan for (M, N, K, epilogue) has a packed-weight form
 int64_t gemm_packed_check(int64_t M, int64_t N, int64_t K, int64_t epilogue) {
   return bfly::gemm_packed_check((int)M, (int)N, (int)K, (int)epilogue);
@@ -1251,6 +1295,18 @@ TORCH_LIBRARY(bfly, m) {
         [](int64_t M, int64_t N, int64_t K, int64_t e) -> int64_t { return bfly::gemm_w8_splitk(M, N, K, e); });
   m.def("gemm_w8_workspace_size(int M, int N, int K) -> int",
         [](int64_t M, int64_t N, int64_t K) -> int64_t { return (int64_t)bfly::gemm_w8_workspace_bytes(M, N, K); });
+  // registered with their kernels as catch-all functions (the Op checks the device), like the
+  // *_check lambdas: the CUDA block below is held to a fixed table by tests/test_ops_refusals_gpu.py
+  m.def("quant_mxfp4(Tensor w, Tensor(a!) code, Tensor(b!) scale) -> ()", &quant_mxfp4);
+  m.def("dequant_mxfp4(Tensor code, Tensor scale, Tensor(a!) out) -> ()", &dequant_mxfp4);
+  m.def("gemm_w4(Tensor x, Tensor code, Tensor scale, Tensor(a!) out, int epilogue, Tensor(b!)? workspace, "
+        "bool any_m=False, int force_sk=0) -> ()", &gemm_w4);
+  m.def("gemm_w4_check(int M, int N, int K, int epilogue) -> int",
+        [](int64_t M, int64_t N, int64_t K, int64_t e) -> int64_t { return bfly::gemm_w4_check(M, N, K, e); });
+  m.def("gemm_w4_splitk(int M, int N, int K, int epilogue) -> int",
+        [](int64_t M, int64_t N, int64_t K, int64_t e) -> int64_t { return bfly::gemm_w4_splitk(M, N, K, e); });
+  m.def("gemm_w4_workspace_size(int M, int N, int K) -> int",
+        [](int64_t M, int64_t N, int64_t K) -> int64_t { return (int64_t)bfly::gemm_w4_workspace_bytes(M, N, K); });
   m.def("gemm_with_plan(Tensor x, Tensor w, Tensor(a!) out, int[] plan, int epilogue, Tensor(b!)? workspace, "
         "Tensor? bias=None, bool packed=False) -> ()");
   m.def("gemm_plan_check(int[] plan, int M, int N, int K, int epilogue, bool packed=False) -> int", &gemm_plan_check);

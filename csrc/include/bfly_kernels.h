@@ -217,6 +217,30 @@ size_t gemm_w8_workspace_bytes(int M, int N, int K);     // split-K slabs of the
 int launch_gemm_w8(const bf16* X, long ldx, const uint8_t* W, const float* scale, int M, int N, int K,
                    int epi, bf16* out, long ldo, float* ws, size_t ws_bytes, hipStream_t stream,
                    bool any_m = false, int force_sk = 0);
+// Sum split-K slabs [sk][M][N] in a fixed order and apply the epilogue (none / SiLU); the slabs
+// hold final f32 sums whatever the weight format, so gemm_w4.hip reduces through it too
+void launch_gemm_w8_reduce(const float* part, int sk, int M, int N, int epi, bf16* out, long ldo,
+                           hipStream_t stream);
+
+// gemm_w4.hip: OCP MXFP4 weight-only linear layers: e2m1 codes [N][K / 2] (element 2 i in the low
+// nibble of byte i), one e8m0 scale byte per 32 elements [N][K / 32]; K % 32 == 0
+void launch_quant_mxfp4(const bf16* w, long ldw, long N, int K, uint8_t* code, uint8_t* scale,
+                        hipStream_t stream);
+// out[n][k] = bf16(value(code[n][k]) * 2^(scale[n][k / 32] - 127)), exact. Scale bytes must lie in
+// 2 .. 252, the range the quantiser writes (every result a normal bf16); 0, 1, 253 - 255 are
+// invalid input to the dequantiser and to the GEMM (0 gives 0, 255 infinity)
+void launch_dequant_mxfp4(const uint8_t* code, const uint8_t* scale, long N, int K, bf16* out, long ldo,
+                          hipStream_t stream);
+// 0 when the native kernel takes the shape (N % 128, K % 128, epilogue none / SiLU, M within
+// its row limit); ops.linear_w4 dequantises and runs the bf16 GEMM otherwise
+int gemm_w4_check(int M, int N, int K, int epi);
+int gemm_w4_splitk(int M, int N, int K, int epi);        // the native plan's split-K factor (0: none)
+size_t gemm_w4_workspace_bytes(int M, int N, int K);     // split-K slabs of the native plan
+// Y = X . dequant(code, scale)^T, epilogue none / SiLU; `any_m` and `force_sk` as in launch_gemm_w8.
+// < 0: not taken.
+int launch_gemm_w4(const bf16* X, long ldx, const uint8_t* W, const uint8_t* scale, int M, int N, int K,
+                   int epi, bf16* out, long ldo, float* ws, size_t ws_bytes, hipStream_t stream,
+                   bool any_m = false, int force_sk = 0);
 
 // attention.hip
 int attn_decode_splits(int max_ctx, int part_tokens);

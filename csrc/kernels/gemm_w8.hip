@@ -343,6 +343,15 @@ gemm_w8_reduce_kernel(const float* __restrict__ part, int SK, int M, int N, int 
 // ---------------------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------------------
+void launch_gemm_w8_reduce(const float* part, int sk, int M, int N, int epi, bf16* out, long ldo,
+                           hipStream_t stream) {
+  const long total = (long)M * ((epi == EPI_SILU ? N / 2 : N) / 4);
+  if (total <= 0) return;
+  long grid = (total + 255) / 256;
+  if (grid > 4096) grid = 4096;
+  gemm_w8_reduce_kernel<<<(int)grid, 256, 0, stream>>>(part, sk, M, N, epi, out, ldo);
+}
+
 struct W8Plan { int mt, nt, sk; };
 
 // Shape contract: N % 128 == 0, K % 128 == 0, epilogue none / SiLU. (`any_m`: skip the row limit.)
@@ -407,12 +416,7 @@ int launch_gemm_w8(const bf16* X, long ldx, const uint8_t* W, const float* scale
     run_w8<MT_, NT_>(X, ldx, W, scale, M, N, K, epi, out, ldo, part, p.sk, stream);
   W8_CASE(1, 2) W8_CASE(2, 2) W8_CASE(3, 2) W8_CASE(4, 2)
 #undef W8_CASE
-  if (part) {
-    const long total = (long)M * ((epi == EPI_SILU ? N / 2 : N) / 4);
-    long grid = (total + 255) / 256;
-    if (grid > 4096) grid = 4096;
-    gemm_w8_reduce_kernel<<<(int)grid, 256, 0, stream>>>(part, p.sk, M, N, epi, out, ldo);
-  }
+  if (part) launch_gemm_w8_reduce(part, p.sk, M, N, epi, out, ldo, stream);
   return 0;
 }
 
