@@ -676,7 +676,7 @@ def dequantize_fp8(code, scale, dtype=None, out=None):
 def linear_w8(x, code, scale, epilogue: str = "none", out=None):
     """y = (x @ float(code).T) * scale with optional fused SwiGLU epilogue: the FP8 e4m3
     weight-only counterpart of `linear` (no bias). Shapes and row counts the native kernel
-    takes (gemm_w8_check) stream the codes once (gemm_w8.hip gemm_w8_kernel); every other one
+    takes (gemm_w8_check) stream the codes once (gemm_w8.hip, wq_gemm_kernel<W8Fmt>); every other one
     widens the codes into the arena's bf16 scratch, runs `linear` on it and scales the result."""
     if not _gpu(x):
         return ref.linear_w8(x, code, scale, epilogue, out)
@@ -743,7 +743,7 @@ def dequantize_mxfp4(code, scale, dtype=None, out=None):
 def linear_w4(x, code, scale, epilogue: str = "none", out=None):
     """y = linear(x, dequantize_mxfp4(code, scale), epilogue): the MXFP4 weight-only
     counterpart of `linear` (no bias). Shapes and row counts the native kernel takes
-    (gemm_w4_check) stream the codes once (gemm_w4.hip gemm_w4_kernel); every other one writes
+    (gemm_w4_check) stream the codes once (gemm_w4.hip, wq_gemm_kernel<W4Fmt>); every other one writes
     the dequantised weights, which bf16 holds exactly, into the arena's scratch and runs
     `linear` on them with the same epilogue. Scale bytes must lie in 2 .. 252 (`dequantize_mxfp4`)."""
     if not _gpu(x):

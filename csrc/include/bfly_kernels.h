@@ -219,7 +219,7 @@ int launch_gemm_w8(const bf16* X, long ldx, const uint8_t* W, const float* scale
                    bool any_m = false, int force_sk = 0);
 // Sum split-K slabs [sk][M][N] in a fixed order and apply the epilogue (none / SiLU); the slabs
 // hold final f32 sums whatever the weight format, so gemm_w4.hip reduces through it too
-void launch_gemm_w8_reduce(const float* part, int sk, int M, int N, int epi, bf16* out, long ldo,
+void launch_gemm_wq_reduce(const float* part, int sk, int M, int N, int epi, bf16* out, long ldo,
                            hipStream_t stream);
 
 // gemm_w4.hip: OCP MXFP4 weight-only linear layers: e2m1 codes [N][K / 2] (element 2 i in the low

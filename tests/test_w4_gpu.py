@@ -142,7 +142,7 @@ def test_exact(N, K, poisoned):
     wd = ref.dequantize_mxfp4(code, scale, torch.float64).to(DEV)
     code, scale = code.to(DEV), scale.to(DEV)
     assert torch.equal(ops.dequantize_mxfp4(code, scale).double(), wd)
-    for M in NATIVE_M + [1024]:
+    for M in NATIVE_M + [200, 1024]:            # one 64-row tile, row-tiled native, dequantise route
         x = torch.randint(-2, 3, (M, K), generator=g).to(torch.bfloat16).to(DEV)
         assert (torch.ops.bfly.gemm_w4_check(M, N, K, 0) == 0) == (M != 1024)
         exact = x.double() @ wd.t()

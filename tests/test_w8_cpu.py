@@ -70,6 +70,43 @@ def test_ref_linear_w8(epi):
         ref.linear_w8(x, code, scale, epilogue="bias")
 
 
+EXACT_SHAPES = [(256, 256), (384, 640), (2048, 1024), (256, 4096)]     # tests/test_w4_gpu.py's
+EXACT_M = [1, 5, 16, 17, 33, 64, 200, 1024]
+
+
+def exact_case(N, K):
+    """Inputs on which linear_w8 has one right answer, bit for bit: codes drawn uniformly with
+    the exponent field forced into 4 .. 10 (a byte outside keeps sign and mantissa and gets
+    exponent 7): 112 distinct codes, every mantissa bit in use, multiples of 2^-6 with
+    0.125 <= |v| <= 15; row scales 2^0 .. 2^3; activations integers in -2 .. 2. Then
+    (|x| @ |w|^T).max() * 64 < 2^24: every partial sum, in any order, is an integer multiple of
+    2^-6 below 2^24 and so exact in f32, the power-of-two scale keeps it exact, and the result
+    is the float64 product rounded to bf16 once. Returns (code, scale, {M: (x, want)})."""
+    g = torch.Generator(device="cpu").manual_seed(N * 7 + K)
+    raw = torch.randint(0, 256, (N, K), generator=g, dtype=torch.uint8)
+    e = (raw >> 3) & 15
+    raw = torch.where((e >= 4) & (e <= 10), raw, (raw & 0x87) | (7 << 3))
+    code = raw.view(torch.float8_e4m3fn)
+    scale = 2.0 ** torch.randint(0, 4, (N,), generator=g).float()
+    w = code.float().double()
+    assert len(w.unique()) == 112 and 0.125 <= float(w.abs().min()) and float(w.abs().max()) == 15
+    assert torch.equal(w * 64, (w * 64).round())
+    cases = {}
+    for M in EXACT_M:
+        x = torch.randint(-2, 3, (M, K), generator=g).to(torch.bfloat16)
+        assert float((x.double().abs() @ w.abs().t()).max()) * 64 < 2 ** 24
+        cases[M] = (x, ((x.double() @ w.t()) * scale.double()).to(torch.bfloat16))
+    return code, scale, cases
+
+
+@pytest.mark.parametrize("N,K", EXACT_SHAPES)
+def test_exact(N, K):
+    code, scale, cases = exact_case(N, K)
+    for M, (x, want) in cases.items():
+        y = ref.linear_w8(x, code, scale)
+        assert y.shape == (M, N) and torch.equal(y, want), f"M={M}: {int((y != want).sum())}/{y.numel()} outputs differ"
+
+
 def _twin(a, cfg, shard=Shard(), comm=None, seed=7):
     """An ordinary model holding the dequantised values of quantised model `a`."""
     b = build_model(cfg, shard, device="cpu", dtype=torch.float32, comm=comm)

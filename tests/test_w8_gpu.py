@@ -17,6 +17,8 @@ from butterfly_amd.engine.sampler import SamplingParams
 from butterfly_amd.models import build_model
 from butterfly_amd.ops import reference as ref
 
+from .test_w8_cpu import EXACT_SHAPES, exact_case
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
@@ -105,6 +107,21 @@ def test_plans():
     assert L.gemm_w8_splitk(1, 8192, 28672, 0) > 1     # 70B down projection at real size
     # llama-tiny's projections
     assert L.gemm_w8_check(8, 1024, 256, 2) == 0 and L.gemm_w8_check(8, 256, 512, 0) == 0
+
+
+@pytest.mark.parametrize("N,K", EXACT_SHAPES)
+def test_exact(N, K, poisoned):
+    """The K permutation and the row scale, bit for bit (test_w8_cpu.exact_case has the inputs):
+    one 64-row tile, the row-tiled native kernel (200 rows) and the dequantise route (1024)."""
+    code, scale, cases = exact_case(N, K)
+    code, scale = code.to(DEV), scale.to(DEV)
+    assert sorted(cases) == sorted(NATIVE_M + [200, 1024])
+    for M, (x, want) in cases.items():
+        assert (torch.ops.bfly.gemm_w8_check(M, N, K, 0) == 0) == (M != 1024)
+        y = ops.linear_w8(x.to(DEV), code, scale)
+        want = want.to(DEV)
+        assert y.shape == (M, N) and torch.equal(y, want), \
+            f"M={M}: {int((y != want).sum())}/{y.numel()} outputs differ"
 
 
 @pytest.mark.parametrize("epi", ["none", "silu"])
