@@ -43,8 +43,8 @@ enum GemmKind : int { kSkinny = 0, kTile = 1, kDec = 3, kBig8 = 4, kMid8 = 5, kB
 //   kBig8       gemm_big8_kernel        -                     -                       -                  - (256 x 256)
 //   kMid8       gemm_mid8_kernel        weight ring depth     activation ring depth   -                  rows   columns
 //                                                             (0: that of the weight)
-//   kBig4       gemm_big4_kernel        -                     -                       -                  - (256 x 256)
-//   kMid4       gemm_mid4_kernel        activation ring depth weight ring depth       -                  rows   columns
+//   kBig4       gemm_wave4_kernel       -                     -                       -                  - (256 x 256)
+//   kMid4       gemm_wave4_kernel       activation ring depth weight ring depth       -                  rows   columns
 //   kTileMixed  gemm_tile_mixed_kernel  pipeline depth        -                       narrow columns     rows   wide columns
 //                                       (0: 3)                                        (96)                      (128)
 //

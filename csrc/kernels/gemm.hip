@@ -42,6 +42,15 @@ typedef __attribute__((address_space(3))) void* lds_ptr_t;
 __constant__ int g_tile_w_nt = 1;
 typedef __attribute__((address_space(1))) void* gbl_ptr_t;
 
+constexpr RowScale kNoRowScale{nullptr, 0, 0.f, 0.f};
+
+// Split-K: split s of `nsplit` owns the K-tiles [split_k_tile(s), split_k_tile(s + 1)): whole
+// tiles, as even as they divide. T: int, or blockIdx.y / gridDim.y as they are.
+template <class T>
+__device__ __forceinline__ int split_k_tile(int ktiles, T split, T nsplit) {
+  return (int)(((long)ktiles * split) / nsplit);
+}
+
 // ---------------------------------------------------------------------------------------
 // Epilogue helpers
 // ---------------------------------------------------------------------------------------
@@ -433,8 +442,7 @@ gemm_tile_kernel(const bf16* __restrict__ X, long ldx, const bf16* __restrict__ 
   const int nsplit = (int)gridDim.y;
 
   const int ktiles = K / kBK;
-  const int kt0 = (int)(((long)ktiles * ksplit) / nsplit);
-  const int kt1 = (int)(((long)ktiles * (ksplit + 1)) / nsplit);
+  const int kt0 = split_k_tile(ktiles, ksplit, nsplit), kt1 = split_k_tile(ktiles, ksplit + 1, nsplit);
   // each W byte read by one workgroup: stream it non-temporally
   const bool w_nt = (GROUPED ? single : M <= BM) && g_tile_w_nt;
 
@@ -516,8 +524,7 @@ __device__ __forceinline__ void tile_body(const bf16* __restrict__ X, long ldx, 
   const int nsplit = (int)gridDim.y;
 
   const int ktiles = K / kBK;
-  const int kt0 = (int)(((long)ktiles * ksplit) / nsplit);
-  const int kt1 = (int)(((long)ktiles * (ksplit + 1)) / nsplit);
+  const int kt0 = split_k_tile(ktiles, ksplit, nsplit), kt1 = split_k_tile(ktiles, ksplit + 1, nsplit);
   // each W byte read by one workgroup: stream it non-temporally
   const bool w_nt = M <= BM && g_tile_w_nt;
 
@@ -671,8 +678,7 @@ gemm_dec_kernel(const bf16* __restrict__ X, long ldx, const bf16* __restrict__ W
   const int m0 = tm * BM, n0 = tn * BN;
   const int nsplit = (int)gridDim.y;
   const int ktiles = K / kBK;
-  const int kt0 = (int)(((long)ktiles * ksplit) / nsplit);
-  const int kt1 = (int)(((long)ktiles * (ksplit + 1)) / nsplit);
+  const int kt0 = split_k_tile(ktiles, ksplit, nsplit), kt1 = split_k_tile(ktiles, ksplit + 1, nsplit);
   const bool w_nt = mtiles == 1 && g_tile_w_nt;   // each weight byte read by one workgroup
 
   f32x4 acc[TI][TJ];
@@ -726,6 +732,14 @@ gemm_dec_kernel(const bf16* __restrict__ X, long ldx, const bf16* __restrict__ W
 // Prefill tiles are walked in GROUP_M super-rows inside each XCD's contiguous range, so the
 // 32 CUs of an XCD share X and W panels in their L2.
 constexpr int kBigGroupM = 8;
+
+struct TileMN { int tm, tn; };   // row tile, column tile of workgroup t (after xcd_remap)
+__device__ __forceinline__ TileMN group_m_walk(int t, int mtiles, int ntiles) {
+  const int per_group = kBigGroupM * ntiles;
+  const int first_m = (t / per_group) * kBigGroupM;
+  const int gsize = min(mtiles - first_m, kBigGroupM);
+  return {first_m + (t % per_group) % gsize, (t % per_group) / gsize};
+}
 
 // ---------------------------------------------------------------------------------------
 // 8-phase big-tile GEMM (prefill): 256x256 tile, BK = 64, two K-tile LDS buffers (128 KiB),
@@ -814,6 +828,14 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t b8_rsrc(const bf16* base, long
                                            0x00020000);
 }
 
+// One 1-KiB LDS-DMA block (16 B per lane) through a buffer descriptor; AUX 2 = non-temporal. A
+// __device__ helper: the builtin's LDS address-space cast inside a kernel template's lambda left
+// the template uninstantiable on the host side, i.e. no launch stub was emitted.
+template <int AUX = 0>
+__device__ __forceinline__ void lds_dma(__amdgpu_buffer_rsrc_t r, char* lds, int voff, int soff) {
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr_t)lds, 16, voff, soff, 0, AUX);
+}
+
 __device__ __forceinline__ void b8_stage_buf(__amdgpu_buffer_rsrc_t ra, __amdgpu_buffer_rsrc_t rb, long ldx,
                                              long ldw, int k0, char* buf, int half, int wid, const B8Dma& d) {
   const bool isA = half == 0 || half == 3;
@@ -823,8 +845,7 @@ __device__ __forceinline__ void b8_stage_buf(__amdgpu_buffer_rsrc_t ra, __amdgpu
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int blk = b8_block(half, 2 * wid + i);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(isA ? ra : rb, (lds_ptr_t)(lds + blk * 1024), 16, isA ? d.a[i] : d.b[i],
-                                             soff, 0, 0);
+    lds_dma(isA ? ra : rb, lds + blk * 1024, isA ? d.a[i] : d.b[i], soff);
   }
 }
 
@@ -856,12 +877,9 @@ gemm_big8_kernel(const bf16* __restrict__ X, long ldx, const bf16* __restrict__ 
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int wr = wid >> 2, wc = wid & 3;
   const int mtiles = (M + BM - 1) / BM, ntiles = N / BN;   // GROUPED: M = tile-list capacity x BM
-  const int t = xcd_remap(blockIdx.x, mtiles * ntiles);
-  const int per_group = kBigGroupM * ntiles;
-  const int grp = t / per_group, first_m = grp * kBigGroupM;
-  const int gsize = min(mtiles - first_m, kBigGroupM);
-  int m0 = (first_m + (t % per_group) % gsize) * BM;
-  const int n0 = ((t % per_group) / gsize) * BN;
+  const TileMN tile = group_m_walk(xcd_remap(blockIdx.x, mtiles * ntiles), mtiles, ntiles);
+  int m0 = tile.tm * BM;
+  const int n0 = tile.tn * BN;
   const bf16* arow[4] = {};
   if constexpr (GROUPED) {
     const int ti = m0 / BM;
@@ -882,8 +900,7 @@ gemm_big8_kernel(const bf16* __restrict__ X, long ldx, const bf16* __restrict__ 
     }
   }
   const int ktiles = K / 64;
-  const int kt0 = (int)(((long)ktiles * blockIdx.y) / gridDim.y);
-  const int kt1 = (int)(((long)ktiles * (blockIdx.y + 1)) / gridDim.y);
+  const int kt0 = split_k_tile(ktiles, blockIdx.y, gridDim.y), kt1 = split_k_tile(ktiles, blockIdx.y + 1, gridDim.y);
   const int nk = kt1 - kt0;   // >= 2 (host check)
 
   f32x4 acc[8][4];
@@ -1007,198 +1024,7 @@ gemm_big8_kernel(const bf16* __restrict__ X, long ldx, const bf16* __restrict__ 
   if (wr == 0) __builtin_amdgcn_s_barrier();   // re-align the groups' barrier counts
   tile_epilogue<8, 4>(acc, m0 + wr * 128, n0 + wc * 64, lane, M, N, epi, bias, out, ldo,
                       part ? part + (long)blockIdx.y * M * N + (long)m0 * N : nullptr, m0,
-                      RowScale{nullptr, 0, 0.f, 0.f});
-}
-
-// ---------------------------------------------------------------------------------------
-// One wave per SIMD, 256x256 tile (plan kind 6, "big4"): 4 waves in 2 x 2, each owning a 128 x
-// 128 output block (8 x 8 mfma_16x16x32 accumulators, 256 registers: the AGPR half of the
-// 512-register file a lone wave gets). Per K-tile (BK = 64) a wave reads 32 fragments (16 KiB
-// of A and B rows) for 128 MFMAs: a third fewer LDS bytes per FLOP than big8's 128 x 64 wave
-// tile, whose fragment reads plus DMA writes fill the LDS port.
-// LDS (160 KiB, all of it): LDS-DMA rings of whole K-tile halves, 3 slots of A (activation
-// rows) and 2 of B (weight rows), 32 KiB each: no staging registers (those pushed the allocator
-// into moving accumulators every K-tile). A gets the deeper ring: an XCD's 32 resident tiles
-// are 8 row tiles x 4 column tiles (GROUP_M walk), so A misses its L2 twice as often as B.
-// One barrier per K-tile, between its two k-steps (ks):
-//   ks 0 of K-tile t: MFMAs on the ks-0 fragments; read the ks-1 fragments of t; DMA A(t+2)
-//     into A slot (t+2) % 3, which K-tile t-1 left before the previous barrier;
-//   own DMA of A(t+1), B(t+1) retired (vmcnt 8: A(t+2) flies), lgkmcnt(0), s_barrier;
-//   ks 1: MFMAs on the ks-1 fragments; read the ks-0 fragments of t+1; DMA B(t+2) into B slot
-//     t % 2 — K-tile t's last reads (its ks-1 fragments) are before this barrier in every wave.
-// Source order is the schedule: each k-step is 16 slots of {4 MFMAs, 1 fragment read, a DMA
-// every other slot} fenced by sched_barrier(0) (cdna_hip_programming.md T19: left alone, the
-// scheduler clusters the memory operations, and a lone wave has nothing to hide the stall
-// behind). A lane's fragments of one (slot, ks) share one address VGPR (immediate offsets: 4
-// VALU per K-tile). Branch-free: past the last K-tile the DMA re-reads it into a slot nobody
-// reads any more (a guard made hipcc wait vmcnt(0) per slot: 3.5x slower).
-// Measured (profiles/r5_gemm_big4/): 1.52-1.55 PF at M = 8192 on the Llama-3-70B projections
-// against 1.39-1.47 for gemm_big8_kernel and 1.53-1.64 for hipBLASLt on the same box. Steps that
-// got it there from 1.0 PF: LDS-DMA rings instead of register staging (no accumulator moves),
-// one loop with no peeled iterations, one fragment read per slot (not two), the loop rotated to
-// end on the barrier, A's DMA moved into ks 0, immediate-offset fragment addresses.
-// ---------------------------------------------------------------------------------------
-constexpr int kB4Threads = 256;
-constexpr int kB4Slot = 256 * 128;                 // one operand half of a K-tile: 32 KiB
-constexpr int kB4LdsBytes = 5 * kB4Slot;           // A slots 0-2, B slots 3-4: 160 KiB
-
-__device__ __forceinline__ void b4_dma(__amdgpu_buffer_rsrc_t r, char* lds, int voff, int soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr_t)lds, 16, voff, soff, 0, 0);
-}
-
-// GROUPED (MoE expert GEMM at prefill scale): as gemm_big8_kernel<true> — M tiles are the
-// entries of the device tile list {expert, first row slot, end slot}, W is offset by the expert,
-// A rows are gathered through grows[slot] by per-lane LDS-DMA offsets from X (rows past the
-// tile's end re-read its last row; their outputs are not stored).
-template <bool GROUPED = false>
-__global__ void __launch_bounds__(kB4Threads) __attribute__((amdgpu_waves_per_eu(1, 1)))
-gemm_big4_kernel(const bf16* __restrict__ X, long ldx, const bf16* __restrict__ W, long ldw,
-                 int M, int N, int K, int epi, const bf16* __restrict__ bias,
-                 bf16* __restrict__ out, long ldo, float* __restrict__ part,
-                 const int* __restrict__ grows = nullptr, const int4* __restrict__ gtiles = nullptr,
-                 const int* __restrict__ gcount = nullptr, long w_estride = 0) {
-  constexpr int BM = 256, BN = 256;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  // wave index in an SGPR: the DMA's LDS destinations (M0) and the fragment row bases are then
-  // scalar (a VGPR wave index cost a readfirstlane + s_nop per DMA instruction)
-  const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wr = wid >> 1, wc = wid & 1;
-  const int mtiles = (M + BM - 1) / BM, ntiles = N / BN;
-  const int t = xcd_remap(blockIdx.x, mtiles * ntiles);
-  const int per_group = kBigGroupM * ntiles;
-  const int grp = t / per_group, first_m = grp * kBigGroupM;
-  const int gsize = min(mtiles - first_m, kBigGroupM);
-  int m0 = (first_m + (t % per_group) % gsize) * BM;
-  const int n0 = ((t % per_group) / gsize) * BN;
-  if constexpr (GROUPED) {
-    const int ti = m0 / BM;
-    if (ti >= *gcount) return;
-    const int4 info = gtiles[ti];
-    W += (long)info.x * w_estride;
-    m0 = info.y;
-    M = info.z;                    // rows [m0, M) of the slot space
-  }
-  const int ktiles = K / 64;
-  const int kt0 = (int)(((long)ktiles * blockIdx.y) / gridDim.y);
-  const int kt1 = (int)(((long)ktiles * (blockIdx.y + 1)) / gridDim.y);
-  const int nk = kt1 - kt0;   // >= 2 (host check)
-
-  // DMA: instruction s (0..7) of wave w fills LDS row block 8 w + s (8 rows x 128 B, lane-
-  // linear); lane L supplies row 8 (8 w + s) + (L >> 3) at the chunk lds_frag expects in
-  // position L & 7: chunk = (L & 7) ^ ((row >> 1) & 7) = (L & 7) ^ ((L >> 4) + 4 (s & 1)) & 7
-  const auto rsa = b8_rsrc(X + (long)m0 * ldx, M - m0, ldx);   // A rows past M read zeros
-  const auto rsb = b8_rsrc(W + (long)n0 * ldw, N - n0, ldw);
-  const int drow = 64 * wid + (lane >> 3);
-  int va[2], vb[2];
-#pragma unroll
-  for (int e = 0; e < 2; ++e) {
-    const int ch = (lane & 7) ^ (((lane >> 4) + 4 * e) & 7);
-    va[e] = (int)((drow * ldx + ch * 8) * 2);
-    vb[e] = (int)((drow * ldw + ch * 8) * 2);
-  }
-  int ga[8] = {};   // GROUPED: byte offsets from X of this lane's gathered rows (at its chunk)
-  const auto rsx = b8_rsrc(X, 1L << 30, 1);
-  if constexpr (GROUPED) {
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const int slot = min(m0 + drow + 8 * q, M - 1);
-      const long src = grows != nullptr ? grows[slot] : slot;
-      ga[q] = (int)((src * ldx + (((lane & 7) ^ (((lane >> 4) + 4 * (q & 1)) & 7)) * 8)) * 2);
-    }
-  }
-  auto dma_a = [&](int k, int slot, int s) {
-    if constexpr (GROUPED)
-      b4_dma(rsx, smem + slot * kB4Slot + (8 * wid + s) * 1024, ga[s], (kt0 + k) * 128);
-    else
-      b4_dma(rsa, smem + slot * kB4Slot + (8 * wid + s) * 1024, va[s & 1], (kt0 + k) * 128 + (int)(8 * s * ldx * 2));
-  };
-  auto dma_b = [&](int k, int slot, int s) {
-    b4_dma(rsb, smem + (3 + slot) * kB4Slot + (8 * wid + s) * 1024, vb[s & 1], (kt0 + k) * 128 + (int)(8 * s * ldw * 2));
-  };
-  const int fr = lane & 15, fq = lane >> 4;
-  // fragment idx 0-7: B rows (output columns) 16 idx, 8-15: A rows 16 (idx - 8), of k-step ks.
-  // lds_frag's swizzle depends on row bits 1-3 = fr bits 1-3 only, so a lane's fragments of one
-  // (slot, ks) share one VGPR address and differ by immediates of 2048 B (16 rows)
-  int lo[2][2];   // [operand A / B][ks] lane byte offset inside a slot
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks) {
-    const int ch = ((ks * 4 + fq) ^ ((fr >> 1) & 7)) * 16;
-    lo[0][ks] = (wr * 128 + fr) * 128 + ch;
-    lo[1][ks] = (wc * 128 + fr) * 128 + ch;
-  }
-  auto rd1 = [&](int sa_, int sb_, int ks, int idx, bf16x8 (&f)[16]) {
-    const char* p = idx < 8 ? smem + (3 + sb_) * kB4Slot + lo[1][ks] + 2048 * idx
-                            : smem + sa_ * kB4Slot + lo[0][ks] + 2048 * (idx - 8);
-    f[idx] = *reinterpret_cast<const bf16x8*>(p);
-  };
-  f32x4 acc[8][8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  // MFMA group n (0..15): output row block i = n / 2, column blocks 4 (n & 1) .. + 3
-  auto mf4 = [&](int n, const bf16x8 (&f)[16]) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int i = n >> 1, j = 4 * (n & 1) + q;
-      acc[i][j] = mfma16(f[j], f[8 + i], acc[i][j]);
-    }
-  };
-  bf16x8 f0[16], f1[16];   // all fragments of k-step 0 / k-step 1
-
-  // prologue: A(0), B(0), A(1), B(1), A(2) (the ring's load order: B(t+2) then A(t+3))
-#pragma unroll
-  for (int s = 0; s < 8; ++s) dma_a(0, 0, s);
-#pragma unroll
-  for (int s = 0; s < 8; ++s) dma_b(0, 0, s);
-#pragma unroll
-  for (int s = 0; s < 8; ++s) dma_a(1, 1, s);
-#pragma unroll
-  for (int s = 0; s < 8; ++s) dma_b(1, 1, s);
-  vm_wait<16>();                      // K-tile 0 landed (own part); A(1), B(1) fly
-  __builtin_amdgcn_s_barrier();
-#pragma unroll
-  for (int idx = 0; idx < 16; ++idx) rd1(0, 0, 0, idx, f0);
-
-  // The loop is rotated so its back edge sits right after the barrier (the compiler puts a
-  // conservative lgkmcnt(0) at a loop header: there it finds nothing outstanding): iteration k =
-  // ks 1 of K-tile k, then ks 0 of K-tile k + 1, then the barrier; the last ks 1 is peeled.
-  auto ks0 = [&](int k, int sa_, int sb_) {   // ks 0 of K-tile k: its ks-1 fragments read
-#pragma unroll
-    for (int n = 0; n < 16; ++n) {
-      mf4(n, f0);
-      // A(k+2) into the slot K-tile k-1 left (its last reads precede the previous barrier)
-      if (n & 1) dma_a(min(k + 2, nk - 1), sa_ == 0 ? 2 : sa_ - 1, n >> 1);
-      rd1(sa_, sb_, 1, n, f1);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    vm_wait<8>();                     // A(k+1), B(k+1) landed; A(k+2) may fly
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-  };
-  auto ks1 = [&](int k, int sa_, int sb_, int sa1_) {   // ks 1 of K-tile k: next ks-0 read, DMA
-    const int kb = min(k + 2, nk - 1);
-#pragma unroll
-    for (int n = 0; n < 16; ++n) {
-      mf4(n, f1);
-      rd1(sa1_, sb_ ^ 1, 0, n, f0);
-      if (n & 1) dma_b(kb, sb_, n >> 1);   // B(k+2) into the slot K-tile k just left
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  };
-  int sa = 0;   // A slot of K-tile k (k % 3)
-  ks0(0, 0, 0);
-  for (int k = 0; k + 1 < nk; ++k) {
-    const int sb = k & 1, sa1 = sa == 2 ? 0 : sa + 1;
-    ks1(k, sa, sb, sa1);
-    ks0(k + 1, sa1, sb ^ 1);
-    sa = sa1;
-  }
-  ks1(nk - 1, sa, (nk - 1) & 1, sa == 2 ? 0 : sa + 1);
-  vm_wait<0>();                       // no LDS-DMA may outlive the workgroup
-  tile_epilogue<8, 8>(acc, m0 + wr * 128, n0 + wc * 128, lane, M, N, epi, bias, out, ldo,
-                      part ? part + (long)blockIdx.y * M * N + (long)m0 * N : nullptr, m0,
-                      RowScale{nullptr, 0, 0.f, 0.f});
+                      kNoRowScale);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1250,14 +1076,6 @@ struct MidCfg {
   static_assert(LDS <= 160 * 1024, "mid rings exceed the LDS");
 };
 
-// One 1-KiB LDS-DMA block through a buffer descriptor (a __device__ helper: the builtin's LDS
-// address-space cast inside the kernel template's lambda left the template uninstantiable on
-// the host side, i.e. no launch stub was emitted)
-template <int AUX>
-__device__ __forceinline__ void mid_dma1(__amdgpu_buffer_rsrc_t r, char* lds, int voff, int soff) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr_t)lds, 16, voff, soff, 0, AUX);
-}
-
 // s_waitcnt vmcnt(n) for a run-time n (the count is an immediate): a jump over constants;
 // n above the largest case waits for less than allowed, i.e. is clamped to a safe (longer) wait
 __device__ __forceinline__ void vm_wait_dyn(int n) {
@@ -1293,8 +1111,8 @@ gemm_mid8_kernel(const bf16* __restrict__ X, long ldx, const bf16* __restrict__ 
   const int tm = t % mtiles, tn = (t / mtiles) % ntiles, ksplit = t / (mtiles * ntiles);
   const int m0 = tm * BM, n0 = tn * BN;
   const int ktiles = K / kBK;
-  const int kt0 = (int)(((long)ktiles * ksplit) / nsplit);
-  const int nk = (int)(((long)ktiles * (ksplit + 1)) / nsplit) - kt0;
+  const int kt0 = split_k_tile(ktiles, ksplit, nsplit), kt1 = split_k_tile(ktiles, ksplit + 1, nsplit);
+  const int nk = kt1 - kt0;
 
   // DMA: wave w moves the 1-KiB blocks w, w + 8, ... of an X / W slot (BM / 8, BN / 8 blocks)
   const auto rsa = b8_rsrc(X + (long)m0 * ldx, M - m0, ldx);
@@ -1319,17 +1137,17 @@ gemm_mid8_kernel(const bf16* __restrict__ X, long ldx, const bf16* __restrict__ 
     char* s = xs + (k % SX) * C::XB;
     const int soff = (kt0 + k) * kBK * 2;
 #pragma unroll
-    for (int i = 0; i < LX; ++i) mid_dma1<0>(rsa, s + (wid + 8 * i) * 1024, vx[i], soff);
+    for (int i = 0; i < LX; ++i) lds_dma(rsa, s + (wid + 8 * i) * 1024, vx[i], soff);
   };
   auto dma_w = [&](int k) {
     char* s = wsm + (k % SW) * C::WB;
     const int soff = (kt0 + k) * (PK ? 256 * kBK * 2 : kBK * 2);
     if (wnt) {
 #pragma unroll
-      for (int i = 0; i < LW; ++i) mid_dma1<2>(rsb, s + (wid + 8 * i) * 1024, vw[i], soff);
+      for (int i = 0; i < LW; ++i) lds_dma<2>(rsb, s + (wid + 8 * i) * 1024, vw[i], soff);
     } else {
 #pragma unroll
-      for (int i = 0; i < LW; ++i) mid_dma1<0>(rsb, s + (wid + 8 * i) * 1024, vw[i], soff);
+      for (int i = 0; i < LW; ++i) lds_dma(rsb, s + (wid + 8 * i) * 1024, vw[i], soff);
     }
   };
   // Loads issued (in order X(j + SX - 1), W(j + SW - 1) per iteration j; the prologue is the
@@ -1404,57 +1222,127 @@ gemm_mid8_kernel(const bf16* __restrict__ X, long ldx, const bf16* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------
-// Mid-M one-wave-per-SIMD GEMM (plan kind 7, "mid4"): big4's structure on 128x128 / 256x128 /
-// 128x256 tiles for the TP-shard and large-batch decode projections (M = 128-512), where
-// split-K fills the chip and each workgroup walks only 8-30 K-tiles. 4 waves in 2 x 2, each
-// owning a (BM/2) x (BN/2) block; per K-tile a wave runs TI x TJ MFMAs per k-step in slots of 4
-// (sched_barrier-fenced, fragment reads and LDS-DMA spread over the slots); LDS-DMA rings of SA
-// activation and SB weight K-tiles (the whole 160 KiB: up to 5 weight K-tiles of lead for the
-// HBM stream); one barrier per K-tile; the loop rotated to end on it (see gemm_big4_kernel).
+// One wave per SIMD GEMM: 4 waves in 2 x 2, each owning a (BM/2) x (BN/2) output block of TI x
+// TJ mfma_16x16x32 accumulators. Two plan kinds run it:
+//  * kind 6 ("big4"), the prefill kernel: the 256x256 tile with rings of 3 A and 2 B K-tiles,
+//    dense or GROUPED. A wave's 128 x 128 block is 8 x 8 accumulators, 256 registers: the AGPR
+//    half of the 512-register file a lone wave gets. Per K-tile (BK = 64) it reads 32 fragments
+//    (16 KiB of A and B rows) for 128 MFMAs: a third fewer LDS bytes per FLOP than big8's 128 x
+//    64 wave tile, whose fragment reads plus DMA writes fill the LDS port.
+//  * kind 7 ("mid4"): 128x128 / 256x128 / 128x256 tiles for the TP-shard and large-batch decode
+//    projections (M = 128-512), where split-K fills the chip and each workgroup walks only 8-30
+//    K-tiles; rings of up to 5 weight K-tiles of lead for the HBM stream.
+// LDS (up to 160 KiB, all of it): LDS-DMA rings of whole K-tile halves, SA slots of A (activation
+// rows, BM x 128 B) then SB of B (weight rows, BN x 128 B): no staging registers (those pushed
+// the allocator into moving accumulators every K-tile). The 256x256 tile gives A the deeper
+// ring: an XCD's 32 resident tiles are 8 row tiles x 4 column tiles (GROUP_M walk), so A misses
+// its L2 twice as often as B.
+// One barrier per K-tile, between its two k-steps (ks):
+//   ks 0 of K-tile t: MFMAs on the ks-0 fragments; read the ks-1 fragments of t; DMA A(t+SA-1)
+//     into A slot (t-1) % SA, which K-tile t-1 left before the previous barrier;
+//   own DMA of A(t+1), B(t+1) retired (counted vmcnt, below), lgkmcnt(0), s_barrier;
+//   ks 1: MFMAs on the ks-1 fragments; read the ks-0 fragments of t+1; DMA B(t+SB) into B slot
+//     t % SB — K-tile t's last reads (its ks-1 fragments) are before this barrier in every wave.
+// Source order is the schedule: each k-step is TI x TJ / 4 slots of {4 MFMAs, the k-step's
+// fragment reads and DMA spread evenly over the slots (256x256: 1 read per slot, a DMA every
+// other slot)} fenced by sched_barrier(0) (cdna_hip_programming.md T19: left alone, the
+// scheduler clusters the memory operations, and a lone wave has nothing to hide the stall
+// behind). A lane's fragments of one (slot, ks) share one address VGPR (immediate offsets: 4
+// VALU per K-tile). Branch-free: past the last K-tile the DMA re-reads it into a slot nobody
+// reads any more (a guard made hipcc wait vmcnt(0) per slot: 3.5x slower).
 // The DMA wait count at the barrier follows the fixed issue order
-//   prologue A(0), B(0), A(1 .. SA-2), B(1 .. SB-1); iteration t: A(t+SA-1) in k-step 0,
-//   B(t+SB) in k-step 1
-// and is computed per iteration (scalar), exact in the first iterations as in the steady state.
+//   prologue A(0), B(0), A(1 .. SA-2), B(1 .. SB-1); iteration t: A(t+SA-1) in ks 0, B(t+SB) in ks 1
+// (Wave4Cfg::in_flight). The kind-7 rings compute it per iteration (scalar, vm_wait_dyn), exact
+// in the first iterations as in the steady state. For the 256x256 tile it is the same in every
+// iteration (A(t+2) may fly), so these instances alone wait with an immediate: no jump table in
+// the prefill loop. (The three SA = 2 rings of kind 7 are constant too, at 0; they keep the
+// run-time form their plans were measured with.) The same instances pass the constant null
+// RowScale to the epilogue, which drops its row-scale paths: kind 6 takes no row scale.
+// GROUPED (MoE expert GEMM at prefill scale, 256x256 only): gemm_big8_kernel<true>'s tile list,
+// the A rows gathered through rows[slot] by per-lane LDS-DMA offsets from X (rows past the tile's
+// end re-read its last row; their outputs are not stored).
+// Measured (profiles/r5_gemm_big4/): 1.52-1.55 PF at M = 8192 on the Llama-3-70B projections
+// against 1.39-1.47 for gemm_big8_kernel and 1.53-1.64 for hipBLASLt on the same box. Steps that
+// got it there from 1.0 PF: LDS-DMA rings instead of register staging (no accumulator moves),
+// one loop with no peeled iterations, one fragment read per slot (not two), the loop rotated to
+// end on the barrier, A's DMA moved into ks 0, immediate-offset fragment addresses.
 // ---------------------------------------------------------------------------------------
-constexpr int kMid4Threads = 256;
+constexpr int kWave4Threads = 256;
 
 template <int BM, int BN, int SA, int SB>
-struct Mid4Cfg {
+struct Wave4Cfg {
   static constexpr int WM = BM / 2, WN = BN / 2, TI = WM / 16, TJ = WN / 16;
-  static constexpr int NS = TI * TJ / 4;            // MFMA slots per k-step
-  static constexpr int NF = TI + TJ;                // fragments per k-step
+  static constexpr int NS = TI * TJ / 4, NF = TI + TJ;   // MFMA slots, fragments per k-step
   static constexpr int NA = BM / 32, NB = BN / 32;  // DMA instructions per thread per K-tile
   static constexpr int ASLOT = BM * 128, BSLOT = BN * 128;
   static constexpr int LDS = SA * ASLOT + SB * BSLOT;
-  static_assert(TJ % 4 == 0 && NA % 2 == 0 && NB % 2 == 0, "mid4 tile shape");
-  static_assert(SA >= 2 && SB >= 2 && LDS <= 160 * 1024, "mid4 rings");
+  static_assert(TJ % 4 == 0 && NA % 2 == 0 && NB % 2 == 0, "wave4 tile shape");
+  static_assert(SA >= 2 && SB >= 2 && LDS <= 160 * 1024, "wave4 rings");
+  // Issue order (header) in per-thread load counts: the prologue's, and up to the last of A(j) / B(j)
+  static constexpr int P = (SA - 1) * NA + SB * NB;
+  static constexpr int idx_a(int j) {
+    return j == 0 ? NA : j <= SA - 2 ? NA + NB + j * NA : P + (j - SA + 1) * (NA + NB) + NA;
+  }
+  static constexpr int idx_b(int j) {
+    return j == 0 ? NA + NB : j <= SB - 1 ? NA + NB + (SA - 2) * NA + j * NB : P + (j - SB) * (NA + NB) + NA + NB;
+  }
+  // At the barrier of K-tile k (after its k-step 0), A(k+1) and B(k+1) must have landed (own
+  // part): the loads issued after the later of them may fly.
+  static constexpr int in_flight(int k) {
+    const int total = P + k * (NA + NB) + NA, a = idx_a(k + 1), b = idx_b(k + 1);
+    return total - (a > b ? a : b);
+  }
+  // From k = max(SA - 1, SB) on, `total` and both indices grow by NA + NB per K-tile, so the
+  // first SA + SB iterations decide whether the count depends on k at all.
+  static constexpr bool in_flight_is_fixed() {
+    for (int k = 1; k <= SA + SB; ++k)
+      if (in_flight(k) != in_flight(0)) return false;
+    return true;
+  }
+  static constexpr bool kPrefill = BM == 256 && BN == 256;   // immediate wait, no row scale
+  static_assert(!kPrefill || in_flight_is_fixed(), "the prefill tile waits with an immediate");
 };
 
-template <int BM, int BN, int SA, int SB, bool PK = false>
-__global__ void __launch_bounds__(kMid4Threads) __attribute__((amdgpu_waves_per_eu(1, 1)))
-gemm_mid4_kernel(const bf16* __restrict__ X, long ldx, const bf16* __restrict__ W, long ldw,
-                 int M, int N, int K, int epi, const bf16* __restrict__ bias,
-                 bf16* __restrict__ out, long ldo, float* __restrict__ part, RowScale rsc) {
-  using C = Mid4Cfg<BM, BN, SA, SB>;
+// What the GROUPED form takes where the dense one takes its row scale.
+struct GroupedTiles {
+  const int* rows;     // token row of each row slot (nullptr: the slot itself)
+  const int4* tiles;   // {expert, first row slot, end row slot, -}
+  const int* count;    // entries in `tiles`; workgroups past them exit
+  long w_estride;      // elements from one expert's weight to the next
+};
+
+template <int BM, int BN, int SA, int SB, bool PK = false, bool GROUPED = false>
+__global__ void __launch_bounds__(kWave4Threads) __attribute__((amdgpu_waves_per_eu(1, 1)))
+gemm_wave4_kernel(const bf16* __restrict__ X, long ldx, const bf16* __restrict__ W, long ldw,
+                  int M, int N, int K, int epi, const bf16* __restrict__ bias,
+                  bf16* __restrict__ out, long ldo, float* __restrict__ part,
+                  std::conditional_t<GROUPED, GroupedTiles, RowScale> tail) {
+  using C = Wave4Cfg<BM, BN, SA, SB>;
   constexpr int TI = C::TI, TJ = C::TJ, NS = C::NS, NF = C::NF, NA = C::NA, NB = C::NB;
+  static_assert(!GROUPED || (C::kPrefill && !PK), "only the row-major 256x256 tile has a grouped form");
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  // wave index in an SGPR: the DMA's LDS destinations (M0) and the fragment row bases are then
+  // scalar (a VGPR wave index cost a readfirstlane + s_nop per DMA instruction)
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wid >> 1, wc = wid & 1;
-  const int mtiles = (M + BM - 1) / BM, ntiles = N / BN;
-  const int t = xcd_remap(blockIdx.x, mtiles * ntiles);
-  const int per_group = kBigGroupM * ntiles;
-  const int grp = t / per_group, first_m = grp * kBigGroupM;
-  const int gsize = min(mtiles - first_m, kBigGroupM);
-  const int m0 = (first_m + (t % per_group) % gsize) * BM;
-  const int n0 = ((t % per_group) / gsize) * BN;
+  const int mtiles = (M + BM - 1) / BM, ntiles = N / BN;   // GROUPED: M = tile-list capacity x BM
+  const TileMN tile = group_m_walk(xcd_remap(blockIdx.x, mtiles * ntiles), mtiles, ntiles);
+  int m0 = tile.tm * BM;
+  const int n0 = tile.tn * BN;
+  if constexpr (GROUPED) {
+    if (tile.tm >= *tail.count) return;
+    const int4 info = tail.tiles[tile.tm];
+    W += (long)info.x * tail.w_estride;
+    m0 = info.y;
+    M = info.z;                    // rows [m0, M) of the slot space
+  }
   const int ktiles = K / 64;
-  const int kt0 = (int)(((long)ktiles * blockIdx.y) / gridDim.y);
-  const int kt1 = (int)(((long)ktiles * (blockIdx.y + 1)) / gridDim.y);
-  const int nk = kt1 - kt0;   // >= 1 (host check)
+  const int kt0 = split_k_tile(ktiles, blockIdx.y, gridDim.y), kt1 = split_k_tile(ktiles, blockIdx.y + 1, gridDim.y);
+  const int nk = kt1 - kt0;   // >= 1 (host check; kind 6: >= 2)
 
   // DMA: instruction s of wave w fills LDS row block NA w + s (A; NB w + s for B), 8 rows x
-  // 128 B lane-linear, lane L supplying row 8 (block) + (L >> 3) at lds_frag's swizzled chunk
-  // (L & 7) ^ ((L >> 4) + 4 (s & 1)) & 7 (NA, NB even)
+  // 128 B lane-linear, lane L supplying row 8 (block) + (L >> 3) at the chunk lds_frag expects in
+  // position L & 7: chunk = (L & 7) ^ ((row >> 1) & 7) = (L & 7) ^ ((L >> 4) + 4 (s & 1)) & 7
   const auto rsa = b8_rsrc(X + (long)m0 * ldx, M - m0, ldx);   // A rows past M read zeros
   // PK: W in the pack_w256 layout (see gemm_mid8_kernel): 128-B rows, 32-KiB K-tiles
   const long wpitch = PK ? 64 : ldw;
@@ -1468,22 +1356,38 @@ gemm_mid4_kernel(const bf16* __restrict__ X, long ldx, const bf16* __restrict__ 
     va[e] = (int)(((8 * NA * wid + (lane >> 3)) * ldx + ch * 8) * 2);
     vb[e] = (int)(((8 * NB * wid + (lane >> 3)) * wpitch + ch * 8) * 2);
   }
+  int ga[NA] = {};   // GROUPED: byte offsets from X of this lane's gathered rows (at its chunk)
+  const auto rsx = b8_rsrc(X, 1L << 30, 1);
+  if constexpr (GROUPED) {
+#pragma unroll
+    for (int q = 0; q < NA; ++q) {
+      const int slot = min(m0 + 8 * NA * wid + (lane >> 3) + 8 * q, M - 1);
+      const long src = tail.rows != nullptr ? tail.rows[slot] : slot;
+      ga[q] = (int)((src * ldx + (((lane & 7) ^ (((lane >> 4) + 4 * (q & 1)) & 7)) * 8)) * 2);
+    }
+  }
   char* const bbase = smem + SA * C::ASLOT;
   auto dma_a = [&](int k, int slot, int s) {
-    b4_dma(rsa, smem + slot * C::ASLOT + (NA * wid + s) * 1024, va[s & 1], (kt0 + k) * 128 + (int)(8 * s * ldx * 2));
+    char* const lds = smem + slot * C::ASLOT + (NA * wid + s) * 1024;
+    if constexpr (GROUPED)
+      lds_dma(rsx, lds, ga[s], (kt0 + k) * 128);
+    else
+      lds_dma(rsa, lds, va[s & 1], (kt0 + k) * 128 + (int)(8 * s * ldx * 2));
   };
   auto dma_b = [&](int k, int slot, int s) {
-    b4_dma(rsb, bbase + slot * C::BSLOT + (NB * wid + s) * 1024, vb[s & 1], (kt0 + k) * kstep + (int)(8 * s * wpitch * 2));
+    lds_dma(rsb, bbase + slot * C::BSLOT + (NB * wid + s) * 1024, vb[s & 1], (kt0 + k) * kstep + (int)(8 * s * wpitch * 2));
   };
   const int fr = lane & 15, fq = lane >> 4;
-  int lo[2][2];   // [A / B][ks] lane byte offset inside a slot (fragments differ by 2048 B)
+  // fragment idx 0 .. TJ-1: B rows (output columns) 16 idx, TJ .. NF-1: A rows 16 (idx - TJ), of
+  // k-step ks. lds_frag's swizzle depends on row bits 1-3 = fr bits 1-3 only, so a lane's
+  // fragments of one (slot, ks) share one VGPR address and differ by immediates of 2048 B (16 rows)
+  int lo[2][2];   // [operand A / B][ks] lane byte offset inside a slot
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks) {
     const int ch = ((ks * 4 + fq) ^ ((fr >> 1) & 7)) * 16;
     lo[0][ks] = (wr * C::WM + fr) * 128 + ch;
     lo[1][ks] = (wc * C::WN + fr) * 128 + ch;
   }
-  // fragment idx 0 .. TJ-1: B (output columns 16 idx), TJ .. NF-1: A (rows 16 (idx - TJ))
   auto rd1 = [&](int sa_, int sb_, int ks, int idx, bf16x8 (&f)[NF]) {
     const char* p = idx < TJ ? bbase + sb_ * C::BSLOT + lo[1][ks] + 2048 * idx
                              : smem + sa_ * C::ASLOT + lo[0][ks] + 2048 * (idx - TJ);
@@ -1501,16 +1405,9 @@ gemm_mid4_kernel(const bf16* __restrict__ X, long ldx, const bf16* __restrict__ 
       acc[i][j] = mfma16(f[j], f[TJ + i], acc[i][j]);
     }
   };
-  bf16x8 f0[NF], f1[NF];
+  bf16x8 f0[NF], f1[NF];   // all fragments of k-step 0 / k-step 1
 
-  // issue-order bookkeeping (per-thread load counts, see the header)
-  constexpr int P = (SA - 1) * NA + SB * NB;
-  auto idx_a = [&](int j) {
-    return j == 0 ? NA : j <= SA - 2 ? NA + NB + j * NA : P + (j - SA + 1) * (NA + NB) + NA;
-  };
-  auto idx_b = [&](int j) {
-    return j == 0 ? NA + NB : j <= SB - 1 ? NA + NB + (SA - 2) * NA + j * NB : P + (j - SB) * (NA + NB) + NA + NB;
-  };
+  // prologue (the header's issue order)
 #pragma unroll
   for (int s = 0; s < NA; ++s) dma_a(0, 0, s);
 #pragma unroll
@@ -1523,11 +1420,14 @@ gemm_mid4_kernel(const bf16* __restrict__ X, long ldx, const bf16* __restrict__ 
   for (int j = 1; j <= SB - 1; ++j)
 #pragma unroll
     for (int s = 0; s < NB; ++s) dma_b(min(j, nk - 1), j, s);
-  vm_wait<P - NA - NB>();            // K-tile 0 landed (own part)
+  vm_wait<C::P - NA - NB>();         // K-tile 0 landed (own part)
   __builtin_amdgcn_s_barrier();
 #pragma unroll
   for (int idx = 0; idx < NF; ++idx) rd1(0, 0, 0, idx, f0);
 
+  // The loop is rotated so its back edge sits right after the barrier (the compiler puts a
+  // conservative lgkmcnt(0) at a loop header: there it finds nothing outstanding): iteration k =
+  // ks 1 of K-tile k, then ks 0 of K-tile k + 1, then the barrier; the last ks 1 is peeled.
   auto ks0 = [&](int k, int sa_, int sb_) {   // k-step 0 of K-tile k; DMA A(k+SA-1); barrier
     const int ka = min(k + SA - 1, nk - 1), slot = sa_ == 0 ? SA - 1 : sa_ - 1;
 #pragma unroll
@@ -1539,9 +1439,8 @@ gemm_mid4_kernel(const bf16* __restrict__ X, long ldx, const bf16* __restrict__ 
       for (int idx = n * NF / NS; idx < (n + 1) * NF / NS; ++idx) rd1(sa_, sb_, 1, idx, f1);
       __builtin_amdgcn_sched_barrier(0);
     }
-    // A(k+1), B(k+1) landed (own part): the loads issued after the later of them may fly
-    const int total = P + k * (NA + NB) + NA;
-    vm_wait_dyn(total - max(idx_a(k + 1), idx_b(k + 1)));
+    if constexpr (C::kPrefill) vm_wait<C::in_flight(0)>();
+    else vm_wait_dyn(C::in_flight(k));
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
   };
@@ -1557,19 +1456,23 @@ gemm_mid4_kernel(const bf16* __restrict__ X, long ldx, const bf16* __restrict__ 
       __builtin_amdgcn_sched_barrier(0);
     }
   };
-  int sa = 0, sb = 0;
+  int sa = 0, sb = 0;   // ring slots of K-tile k (a 2-slot B ring steps by a toggle: 2 SALU fewer per K-tile)
   ks0(0, 0, 0);
   for (int k = 0; k + 1 < nk; ++k) {
-    const int sa1 = sa == SA - 1 ? 0 : sa + 1, sb1 = sb == SB - 1 ? 0 : sb + 1;
+    const int sa1 = sa == SA - 1 ? 0 : sa + 1, sb1 = SB == 2 ? sb ^ 1 : sb == SB - 1 ? 0 : sb + 1;
     ks1(k, sa, sb, sa1, sb1);
     ks0(k + 1, sa1, sb1);
     sa = sa1;
     sb = sb1;
   }
-  ks1(nk - 1, sa, sb, sa == SA - 1 ? 0 : sa + 1, sb == SB - 1 ? 0 : sb + 1);
+  ks1(nk - 1, sa, sb, sa == SA - 1 ? 0 : sa + 1, SB == 2 ? sb ^ 1 : sb == SB - 1 ? 0 : sb + 1);
   vm_wait<0>();                       // no LDS-DMA may outlive the workgroup
-  tile_epilogue<TI, TJ>(acc, m0 + wr * C::WM, n0 + wc * C::WN, lane, M, N, epi, bias, out, ldo,
-                        part ? part + (long)blockIdx.y * M * N + (long)m0 * N : nullptr, m0, rsc);
+  float* const slab = part ? part + (long)blockIdx.y * M * N + (long)m0 * N : nullptr;
+  const int r0 = m0 + wr * C::WM, c0 = n0 + wc * C::WN;
+  if constexpr (C::kPrefill)   // the constant null row scale: the epilogue's row-scale paths fold away
+    tile_epilogue<TI, TJ>(acc, r0, c0, lane, M, N, epi, bias, out, ldo, slab, m0, kNoRowScale);
+  else
+    tile_epilogue<TI, TJ>(acc, r0, c0, lane, M, N, epi, bias, out, ldo, slab, m0, tail);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1590,7 +1493,6 @@ struct GemmArgs {
   bool row_scale;  // the caller passed `rsc`: only kinds with a row-scale epilogue may run
 };
 using GemmLauncher = void (*)(const GemmArgs&, int sk, hipStream_t);
-constexpr RowScale kNoRowScale{nullptr, 0, 0.f, 0.f};
 
 static float* slabs(const GemmArgs& a, int sk) { return sk > 1 ? a.ws + kCounterBytes / sizeof(float) : nullptr; }
 
@@ -1661,16 +1563,13 @@ static void run_big8(const GemmArgs& a, int sk, hipStream_t stream) {
                                         nullptr, nullptr, nullptr, 0);
 }
 
-static void run_big4(const GemmArgs& a, int sk, hipStream_t stream) {
-  launch_dense<gemm_big4_kernel<false>>(dim3(tiles_of(a, 256, 256), sk), kB4Threads, kB4LdsBytes, a, sk, stream,
-                                        nullptr, nullptr, nullptr, 0);
-}
-
 template <int BM, int BN, int SA, int SB, bool PK>
-static void run_mid4(const GemmArgs& a, int sk, hipStream_t stream) {
-  launch_dense<gemm_mid4_kernel<BM, BN, SA, SB, PK>>(dim3(tiles_of(a, BM, BN), sk), kMid4Threads,
-                                                     Mid4Cfg<BM, BN, SA, SB>::LDS, a, sk, stream, a.rsc);
+static void run_wave4(const GemmArgs& a, int sk, hipStream_t stream) {
+  launch_dense<gemm_wave4_kernel<BM, BN, SA, SB, PK>>(dim3(tiles_of(a, BM, BN), sk), kWave4Threads,
+                                                      Wave4Cfg<BM, BN, SA, SB>::LDS, a, sk, stream, a.rsc);
 }
+// Kind 6, named ahead of find_mid4's instances: the place gemm_big4_kernel had in the code object.
+constexpr GemmLauncher run_big4 = &run_wave4<256, 256, 3, 2, false>;
 
 template <int BM, int BN, int SX, int SW, bool PK>
 static void run_mid8(const GemmArgs& a, int sk, hipStream_t stream) {
@@ -1794,7 +1693,7 @@ static GemmPlan plan_gemm_heuristic(int M, int N, int K) {
     return p;
   }
   if (M > 256 && N % 256 == 0 && K % 64 == 0) {
-    // prefill / large batch: the 256x256 one-wave-per-SIMD tile (gemm_big4_kernel: 1.52-1.55
+    // prefill / large batch: the 256x256 one-wave-per-SIMD tile (gemm_wave4_kernel: 1.52-1.55
     // PF at M = 8192 on the 70B projections, 6-10 % over the 8-phase gemm_big8_kernel and ahead
     // of it at M = 256-2048 too, profiles/r5_gemm_big4/); split K only when the tile grid cannot
     // fill the 256 CUs
@@ -1846,7 +1745,7 @@ size_t gemm_workspace_bytes(int M, int N, int K) {
 static GemmLauncher find_mid4(const GemmPlan& p, bool packed) {
 #define MID4_CASE(BM_, BN_, SA_, SB_)                              \
   if (p.bm == BM_ && p.bn == BN_ && p.mt == SA_ && p.nt == SB_) \
-    return packed ? &run_mid4<BM_, BN_, SA_, SB_, true> : &run_mid4<BM_, BN_, SA_, SB_, false>;
+    return packed ? &run_wave4<BM_, BN_, SA_, SB_, true> : &run_wave4<BM_, BN_, SA_, SB_, false>;
   MID4_CASE(128, 128, 4, 6) MID4_CASE(128, 128, 3, 7) MID4_CASE(128, 128, 2, 8)
   MID4_CASE(256, 128, 3, 4) MID4_CASE(256, 128, 2, 6) MID4_CASE(128, 256, 4, 3) MID4_CASE(128, 256, 2, 4)
 #undef MID4_CASE
@@ -1954,7 +1853,7 @@ static int resolve_plan(const GemmPlan& p, int M, int N, int K, int epi, bool ro
     case kBig8:
     case kBig4:   // every split needs >= 2 K-tiles of 64
       if (N % 256 != 0 || K % 64 != 0 || K / 64 < 2 * p.sk) return -1;
-      fn = p.kind == kBig8 ? &run_big8 : &run_big4;
+      fn = p.kind == kBig8 ? &run_big8 : run_big4;
       break;
     case kMid4:
       if (N % p.bn != 0 || K % 64 != 0 || K / 64 < p.sk) return -1;
@@ -2119,8 +2018,9 @@ int launch_gemm_grouped(const bf16* X, long ldx, const bf16* W, long ldw, long w
       launch<gemm_big8_kernel<true>>(grid, kB8Threads, kB8LdsBytes, stream, X, ldx, W, ldw, max_tiles * 256, N, K,
                                      epi, no_bias, out, ldo, no_part, rows, tiles, count, w_estride);
     else
-      launch<gemm_big4_kernel<true>>(grid, kB4Threads, kB4LdsBytes, stream, X, ldx, W, ldw, max_tiles * 256, N, K,
-                                     epi, no_bias, out, ldo, no_part, rows, tiles, count, w_estride);
+      launch<gemm_wave4_kernel<256, 256, 3, 2, false, true>>(
+          grid, kWave4Threads, Wave4Cfg<256, 256, 3, 2>::LDS, stream, X, ldx, W, ldw, max_tiles * 256, N, K, epi, no_bias,
+          out, ldo, no_part, GroupedTiles{rows, tiles, count, w_estride});
     return 0;
   }
   const auto tile = [&](auto bm_) {

@@ -491,13 +491,13 @@ def test_gate_scaled_silu_epilogue(M, El, e0, E, H, F):
 
 
 @pytest.mark.parametrize("M,N,K", [(600, 512, 1024), (256, 768, 192), (77, 256, 128), (1000, 1280, 4096),
-                                   (300, 512, 256), (520, 512, 128)])
+                                   (300, 512, 256), (520, 512, 128), (257, 256, 320)])
 @pytest.mark.parametrize("kind", [4, 6])
 @pytest.mark.parametrize("epi", ["none", "bias", "silu"])
 def test_gemm_big_tile(M, N, K, epi, kind):
     """256x256 prefill kernels (plan kind 4: 8-phase, 8 waves; kind 6: one wave per SIMD):
-    ragged M, the minimum of two 64-deep K-tiles per split, uneven split-K, all epilogues,
-    asymmetric operands."""
+    ragged M, the minimum of two 64-deep K-tiles per split, uneven split-K (5 K-tiles as 2 + 3:
+    kind 6's A ring wraps under a one-row last tile), all epilogues, asymmetric operands."""
     x = _bf(M, K, seed=60)
     w = _bf(N, K, scale=1.0 / math.sqrt(K), seed=61)
     b = _bf(N, seed=62) if epi == "bias" else None

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Prefill GEMM A/B on the Llama-3-70B projections: gemm_big8_kernel (plan kind 4: 8 waves,
-8-phase BK 64) and gemm_big4_kernel (plan kind 6: one wave per SIMD, 128 x 128 wave tiles,
-slot-fenced schedule) vs torch.matmul (hipBLASLt, yardstick only; not used by the framework).
+8-phase BK 64) and gemm_wave4_kernel<256, 256, 3, 2> (plan kind 6: one wave per SIMD, 128 x 128
+wave tiles, slot-fenced schedule) vs torch.matmul (hipBLASLt, yardstick only; not used by the
+framework).
 The round-3 variants that lost are recorded in profiles/r3_gemm_prefill_pmc.md.
 
 Random uniform [-1, 1) operands (cdna_hip_programming.md §5.4 rule 25: zero-filled data clocks
@@ -22,7 +23,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from butterfly_amd import ops  # noqa: E402
 from butterfly_amd.ops import reference as ref  # noqa: E402
 
-KINDS = (4, 6)   # 4: gemm_big8_kernel (8 waves, the default); 6: gemm_big4_kernel (one wave per SIMD)
+KINDS = (4, 6)   # 4: gemm_big8_kernel (8 waves, the default); 6: gemm_wave4_kernel (one wave per SIMD)
 SHAPES = [("qkv", 10240, 8192, "none"), ("o", 8192, 8192, "none"), ("gate_up", 57344, 8192, "silu"),
           ("down", 8192, 28672, "none")]
 

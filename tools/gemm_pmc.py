@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Prefill GEMM variants on one Llama-3-70B shape (QKV, 8192 tokens), a few serialized calls
 each, for rocprofv3 PMC passes (counters per kernel name: gemm_big8_kernel, plan kind 4;
-gemm_big4_kernel, plan kind 6) and
+gemm_wave4_kernel<256, 256, 3, 2>, plan kind 6) and
 hipBLASLt as the yardstick."""
 import os
 import sys
