@@ -145,6 +145,15 @@ class LLM:
         self.last_generate_s = time.perf_counter() - t0
         return outs
 
+    def load_lora(self, name: str, path) -> int:
+        """Load a LoRA adapter directory (butterfly-lora v1 or PEFT) under `name`; requests pick
+        it with SamplingParams.lora. Every rank calls it (SPMD). Returns the slot."""
+        return self.engine.load_lora(name, path)
+
+    def unload_lora(self, name: str) -> None:
+        """Free the adapter's slot (refused while an unfinished request uses it)."""
+        self.engine.unload_lora(name)
+
     def metrics(self) -> dict:
         return self.engine.metrics.summary()
 

@@ -4,7 +4,8 @@
              [--schedule RANK]   (that rank's decode-step communication program)
   generate   --model llama-tiny|CKPT_DIR --prompt "..." [--max-tokens N] [--plan auto|tp2] [--logprobs N]
              [--presence-penalty X] [--frequency-penalty X] [--repetition-penalty X]
-  serve      --model ... [--host 127.0.0.1 --port 8000]         (run under `launch` for N GPUs)
+             [--lora NAME=DIR ... --use-lora NAME]   (LoRA adapter directories; the one the prompts run with)
+  serve      --model ... [--host 127.0.0.1 --port 8000] [--lora NAME=DIR ...]   (run under `launch` for N GPUs)
   bench      ...                                                  (forwards to bench.py)
   launch     -n 8 -- <program args...>                            one process per GPU
   ckpt       convert-hf SRC DST | reshard SRC DST --gpus N [--strategy ...] | inspect DIR
@@ -29,6 +30,22 @@ def _strategy(s: str | None):
         k = part.rstrip("0123456789")
         d[k] = int(part[len(k):])
     return d
+
+
+def _lora_args(items) -> dict:
+    """--lora NAME=DIR (repeatable) -> {name: directory}."""
+    out = {}
+    for it in items or []:
+        name, sep, path = it.partition("=")
+        if not sep or not name or not path or name in out:
+            raise SystemExit(f"--lora expects NAME=DIR with distinct names, got {it!r}")
+        out[name] = path
+    return out
+
+
+def _lora_config(loras: dict, max_rank: int) -> dict:
+    """EngineConfig fields: one slot per adapter named on the command line (none: the BFLY_MAX_LORAS flag)."""
+    return dict(max_loras=len(loras) or None, max_lora_rank=max_rank)
 
 
 def cmd_partition(a) -> int:
@@ -73,15 +90,21 @@ def cmd_generate(a) -> int:
     from .engine import state
 
     snap_every = a.snapshot_every if a.snapshot_dir else 0
+    loras = _lora_args(a.lora)
+    if a.use_lora is not None and a.use_lora not in loras:
+        raise SystemExit(f"--use-lora {a.use_lora!r}: no --lora {a.use_lora}=DIR given")
     llm = LLM(a.model, plan=_strategy(a.plan),
               engine_config=EngineConfig(max_batch=8, max_seq_len=a.max_seq_len, use_graphs=not a.no_graphs,
                                          snapshot_dir=a.snapshot_dir, snapshot_every=snap_every,
-                                         weight_dtype=a.weight_dtype),
+                                         weight_dtype=a.weight_dtype, **_lora_config(loras, a.max_lora_rank)),
               tokenizer=a.tokenizer)
+    for name, path in loras.items():
+        llm.load_lora(name, path)
     prompts = a.prompt or ["Hello"]
     params = SamplingParams(max_tokens=a.max_tokens, temperature=a.temperature, seed=a.seed, ignore_eos=True,
                             logprobs=a.logprobs, presence_penalty=a.presence_penalty,
-                            frequency_penalty=a.frequency_penalty, repetition_penalty=a.repetition_penalty)
+                            frequency_penalty=a.frequency_penalty, repetition_penalty=a.repetition_penalty,
+                            lora=a.use_lora)
     # a restart is BFLY_RESTART (launch --max-restarts) or torchrun's TORCHELASTIC_RESTART_COUNT
     restart = max(int(os.environ.get("BFLY_RESTART", "0") or 0),
                   int(os.environ.get("TORCHELASTIC_RESTART_COUNT", "0") or 0))
@@ -120,9 +143,13 @@ def cmd_serve(a) -> int:
     from .config import EngineConfig
     from .server import serve
 
+    loras = _lora_args(a.lora)
     llm = LLM(a.model, plan=_strategy(a.plan), tokenizer=a.tokenizer,
               engine_config=EngineConfig(max_batch=a.max_batch, max_seq_len=a.max_seq_len,
-                                         weight_dtype=a.weight_dtype))
+                                         weight_dtype=a.weight_dtype,
+                                         **_lora_config(loras, a.max_lora_rank)))
+    for name, path in loras.items():
+        llm.load_lora(name, path)
     serve(llm, a.host, a.port)
     return 0
 
@@ -173,10 +200,13 @@ def cmd_info(a) -> int:
     import torch
 
     from . import ops
+    from .config import EngineConfig
     from .utils import flags
 
     info = {"torch": torch.__version__, "hip": torch.version.hip, "gpu": torch.cuda.is_available(),
             "kernels_loaded": ops.load_library(), "kernel_lib": ops.library_path(), "weight_dtypes": list(WEIGHT_DTYPES),
+            "lora": {"slots": flags.get("BFLY_MAX_LORAS"), "max_rank": EngineConfig().max_lora_rank,
+                     "slot_ranks": list(ops.LORA_RANKS)},
             "flags": flags.dump()}
     if torch.cuda.is_available():
         p = torch.cuda.get_device_properties(0)
@@ -222,6 +252,10 @@ def main(argv=None) -> int:
     g.add_argument("--weight-dtype", default="auto", choices=["auto", *WEIGHT_DTYPES],
                    help="dense projection weights: bf16, fp8 (weight-only e4m3) or mxfp4 (weight-only OCP MXFP4); "
                         "auto = BFLY_WEIGHT_DTYPE")
+    g.add_argument("--lora", action="append", metavar="NAME=DIR",
+                   help="load a LoRA adapter directory (butterfly-lora v1 or PEFT) under NAME; repeatable")
+    g.add_argument("--use-lora", default=None, metavar="NAME", help="run the prompts with this adapter")
+    g.add_argument("--max-lora-rank", type=int, default=16, help="largest adapter rank the slots hold (up to 64)")
     g.add_argument("--snapshot-dir", default=None,
                    help="write request-state snapshots here; a restarted job (launch --max-restarts) resumes from them")
     g.add_argument("--snapshot-every", type=int, default=4, help="engine steps between snapshots")
@@ -238,6 +272,9 @@ def main(argv=None) -> int:
                    help="dense projection weights: bf16, fp8 (weight-only e4m3) or mxfp4 (weight-only OCP MXFP4); "
                         "auto = BFLY_WEIGHT_DTYPE")
     s.set_defaults(fn=cmd_serve)
+    s.add_argument("--lora", action="append", metavar="NAME=DIR",
+                   help="serve a LoRA adapter directory under NAME (a request's \"model\" field selects it); repeatable")
+    s.add_argument("--max-lora-rank", type=int, default=16, help="largest adapter rank the slots hold (up to 64)")
     b = sub.add_parser("bench", add_help=False)
     b.add_argument("rest", nargs=argparse.REMAINDER)
     b.set_defaults(fn=lambda a: subprocess.call([sys.executable, os.path.join(

@@ -229,6 +229,11 @@ class EngineConfig:
     # e2m1 codes with one e8m0 scale per 32 elements along K, 4.25 bits per weight). "auto": the
     # BFLY_WEIGHT_DTYPE flag.
     weight_dtype: str = "auto"          # "auto" or one of WEIGHT_DTYPES
+    # LoRA adapters served beside the base model, every request picking its own
+    # (SamplingParams.lora): `max_loras` slots of rank up to `max_lora_rank` are allocated before
+    # the KV cache is sized. None: the BFLY_MAX_LORAS flag; 0: off (nothing allocated or launched).
+    max_loras: Optional[int] = None
+    max_lora_rank: int = 16
     # context-parallel prefill across data-parallel replicas (pp == 1, no EP): a prompt of at
     # least this many tokens is prefilled by ALL dp replicas together (ring or Ulysses
     # attention, parallel/context_parallel.py), its K/V collected in the cache of the replica

@@ -39,6 +39,9 @@ class ForwardBatch:
     cu_fresh: Optional[torch.Tensor] = None
     max_fresh: int = 0
     max_paged: int = 0
+    # LoRA step: int32 [T] adapter slot of every row (outside [0, slots): none). None: no row
+    # of the step has an adapter and the forward pass is the plain one.
+    lora_idx: Optional[torch.Tensor] = None
 
     @property
     def num_tokens(self) -> int:
@@ -57,7 +60,7 @@ class ForwardBatch:
                             mv(self.ctx_lens), self.max_ctx, mv(self.logits_idx), self.ep_tokens,
                             self.ep_alltoall, self.cp, self.num_decode, self.prefix_lens,
                             mv(self.prefix_cu), mv(self.prefix_tables), self.split_seqs, self.split_rows,
-                            mv(self.cu_fresh), self.max_fresh, self.max_paged)
+                            mv(self.cu_fresh), self.max_fresh, self.max_paged, mv(self.lora_idx))
 
 
 def make_prefill_batch(prompts: list[list[int]], slots: list[list[int]], device="cpu",

@@ -150,6 +150,24 @@ class LLMEngine:
                 torch.cuda.empty_cache()
         elif getattr(self.model, "weight_dtype", "bf16") != "bf16":
             self.weight_dtype = self.model.weight_dtype      # handed an already quantised model
+        # ---- LoRA adapter tables (before the KV cache is sized too, so its budget sees them)
+        self.max_loras = int(flags.get("BFLY_MAX_LORAS") if engine_cfg.max_loras is None else engine_cfg.max_loras)
+        self.loras: dict[str, int] = {}          # adapter name -> slot
+        self._lora_info: dict[str, dict] = {}    # adapter name -> {"rank", "alpha", "scale", "path"}
+        if self.max_loras < 0:
+            raise ValueError(f"max_loras must be >= 0 (got {self.max_loras})")
+        if self.max_loras:
+            if mesh.pp > 1:
+                raise ValueError("LoRA adapters are not supported with pipeline parallelism (pp > 1)")
+            if engine_cfg.cp_prefill_min_tokens > 0:
+                raise ValueError("LoRA adapters are not supported with context-parallel prefill "
+                                 "(cp_prefill_min_tokens > 0)")
+            if not self.model.lora_a:
+                self.model.enable_lora(self.max_loras, engine_cfg.max_lora_rank)
+            if self.device.type == "cuda":
+                ops.reserve_lora_workspace(self.device, max(engine_cfg.max_prefill_tokens, engine_cfg.max_batch,
+                                                            *engine_cfg.graph_batch_sizes),
+                                           self.model.lora_max_j())
         # ---- KV cache sizing ------------------------------------------------------------
         bs = engine_cfg.block_size
         self.kv_dtype = kv_cache_dtype(engine_cfg.kv_cache_dtype, self.model.dtype)
@@ -238,6 +256,8 @@ class LLMEngine:
             buckets.append(self.scheduler.group_batch)    # a full group replays one graph
         self.runner = ModelRunner(self.model, self.kv, engine_cfg.max_seq_len, engine_cfg.use_graphs,
                                   buckets, max_batch=engine_cfg.max_batch)
+        if self.max_loras:
+            self.runner.lora_of = self.lora_of
         if self.async_pp and flags.get("BFLY_GRAPH_SAMPLING") and self.comm.capturable("tp"):
             # the last stage's decode graphs end with the sampler on per-request temperatures /
             # seeds staged with the other inputs: one replay per step yields the tokens
@@ -329,10 +349,11 @@ class LLMEngine:
             raise ValueError(f"prompt ({len(prompt)}) + max_tokens ({params.max_tokens}) exceeds max_seq_len")
         self._check_logprobs(params)
         self._check_penalties(params)
+        adapter = self._resolve_lora(params) >= 0
         self.requests[rid] = Request(rid, list(prompt), params, arrival=time.perf_counter())
         if self.cp_min and len(prompt) >= self.cp_min:
             self._cp_queue.append(rid)        # prefilled by the DP group together (_cp_step)
-        elif self.prefix_cache:
+        elif self.prefix_cache and not adapter:
             self.scheduler.add(rid, len(prompt), params.max_tokens, list(prompt))
         else:
             self.scheduler.add(rid, len(prompt), params.max_tokens)
@@ -417,6 +438,53 @@ class LLMEngine:
                                       q.params.presence_penalty) for q in reqs]).to(self.device, non_blocking=True)
         return self.sampler.penalise(logits, st.hist, meta, params)
 
+    # ---- LoRA adapters ----------------------------------------------------------------------
+    def _resolve_lora(self, params: SamplingParams) -> int:
+        """Slot of the adapter a request names (-1: none); ValueError for one that is not loaded."""
+        name = params.lora
+        if name is None:
+            return -1
+        if not self.max_loras:
+            raise ValueError(f"request names LoRA adapter {name!r} but the engine runs without LoRA (max_loras = 0)")
+        if name not in self.loras:
+            raise ValueError(f"unknown LoRA adapter {name!r} (loaded: {sorted(self.loras) or 'none'})")
+        return self.loras[name]
+
+    def lora_of(self, rid: int) -> int:
+        """Adapter slot of a request, -1 for the base model (host bookkeeping only)."""
+        req = self.requests.get(rid)
+        name = req.params.lora if req is not None else None
+        return -1 if name is None else self.loras.get(name, -1)
+
+    def load_lora(self, name: str, path) -> int:
+        """Load the adapter directory `path` (ckpt/lora.py: butterfly-lora v1 or PEFT) into a free
+        slot under `name`. SPMD: every rank calls it. The copies into the slot run on the compute
+        stream, behind the steps in flight. Returns the slot."""
+        from ..ckpt import lora as lora_ckpt
+
+        if not self.max_loras:
+            raise ValueError("load_lora: the engine runs without LoRA (max_loras = 0)")
+        if name in self.loras:
+            raise ValueError(f"load_lora: an adapter named {name!r} is already loaded")
+        free = sorted(set(range(self.max_loras)) - set(self.loras.values()))
+        if not free:
+            raise ValueError(f"load_lora: all {self.max_loras} adapter slots are in use")
+        ad = lora_ckpt.load_lora(path)
+        self.model.load_lora(free[0], ad.tensors, ad.scale)
+        self.loras[name] = free[0]
+        self._lora_info[name] = {"rank": ad.rank, "alpha": ad.alpha, "scale": ad.scale, "path": str(path)}
+        return free[0]
+
+    def unload_lora(self, name: str) -> None:
+        """Free an adapter's slot; refused while an unfinished request uses it."""
+        if name not in self.loras:
+            raise ValueError(f"unload_lora: unknown LoRA adapter {name!r}")
+        users = [r.rid for r in self.requests.values() if r.params.lora == name and not (r.finished and r.sched_done)]
+        if users:
+            raise ValueError(f"unload_lora: adapter {name!r} is in use by unfinished requests {users[:8]}")
+        self.model.clear_lora(self.loras.pop(name))
+        self._lora_info.pop(name, None)
+
     def _admit_resumed(self, req: Request) -> None:
         """Scheduler admission of a restored request (engine/state.py): its prompt plus the
         tokens it already generated are prefilled as one sequence, the rest is generated."""
@@ -426,7 +494,7 @@ class LLMEngine:
         remaining = req.params.max_tokens - len(req.output)
         if len(toks) + remaining > self.ecfg.max_seq_len:
             raise ValueError(f"restored request {req.rid} exceeds max_seq_len")
-        if self.prefix_cache:
+        if self.prefix_cache and self._resolve_lora(req.params) < 0:
             self.scheduler.add(req.rid, len(toks), remaining, list(toks))
         else:
             self.scheduler.add(req.rid, len(toks), remaining)

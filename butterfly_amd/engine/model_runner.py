@@ -56,18 +56,21 @@ class _DecodeGraph:
     stage's graph ends with the sampling kernel (and the TP merge) on those per-request
     temperatures / seeds: `ids` are the step's tokens, one replay per step."""
 
-    def __init__(self, bucket: int, max_blocks: int, device, hidden: int, first: bool):
+    def __init__(self, bucket: int, max_blocks: int, device, hidden: int, first: bool, lora: bool = False):
         b = bucket
         self.bucket = bucket
         self.max_blocks = max_blocks
         self.off_t = b * (4 + max_blocks)                 # temperatures
         self.off_s = (self.off_t + b + 1) // 2 * 2        # seeds: 8-byte aligned int32 offset
-        # initial state built on the host and copied once: padding rows have no cache slot (-1)
-        # and context 1 (no torch fill kernels on the device)
-        init = torch.zeros(self.off_s + 2 * b, dtype=torch.int32)
+        self.off_l = self.off_s + 2 * b                   # adapter slots (graphs of LoRA steps only)
+        # initial state built on the host and copied once: padding rows have no cache slot (-1),
+        # context 1 and no adapter (-1) (no torch fill kernels on the device)
+        init = torch.zeros(self.off_l + (b if lora else 0), dtype=torch.int32)
         init[2 * b:3 * b] = -1
         init[3 * b:4 * b] = 1
+        init[self.off_l:] = -1
         self.inbuf = init.to(device)
+        self.lora_idx = self.inbuf[self.off_l:self.off_l + b] if lora else None
         self.input_ids = self.inbuf[0:b]
         self.positions = self.inbuf[b:2 * b]
         self.slots = self.inbuf[2 * b:3 * b]
@@ -102,7 +105,12 @@ class ModelRunner:
             os.environ.get("BFLY_DISABLE_GRAPHS", "0") != "1"
         self.buckets = sorted(graph_batch_sizes or [1, 2, 4, 8, 16, 32, 64])
         self.graphs: dict[int, _DecodeGraph] = {}
+        # a second set per bucket for steps with adapter rows (static inputs with a lora_idx
+        # region), captured on demand; steps without adapter rows replay `graphs` untouched
+        self.lora_graphs: dict[int, _DecodeGraph] = {}
+        self.lora_of = None            # rid -> adapter slot or -1 (set by an engine with LoRA on)
         self.eager_buckets: set = set()
+        self.lora_eager: set = set()
         self.pool = None
         self.post_fn = post_fn
         # BFLY_PROGRAM_CHECK: rows -> the in-stage collectives of this rank's decode-step
@@ -132,6 +140,17 @@ class ModelRunner:
     def bucket_of(self, n: int) -> int:
         return self.buckets[bisect.bisect_left(self.buckets, n)]
 
+    def _lora_rows(self, sids, counts=None) -> Optional[np.ndarray]:
+        """Adapter slot of every row of a step (sequence `sids[i]` holding counts[i] rows, default
+        one), or None when no sequence of the step has an adapter."""
+        if self.lora_of is None:
+            return None
+        slots = [self.lora_of(s) for s in sids]
+        if not any(s >= 0 for s in slots):
+            return None
+        a = np.asarray(slots, dtype=np.int32)
+        return a if counts is None else np.repeat(a, np.asarray(counts, dtype=np.int64))
+
     # ------------------------------------------------------------------------------------
     def prefill_batch(self, plan, tokens_of) -> ForwardBatch:
         """Batch for a prefill plan; tokens_of(sid) -> full token list to (re)compute."""
@@ -146,7 +165,9 @@ class ModelRunner:
             last.append(cu[-1] - 1)
         dev = self.device
         i32 = dict(dtype=torch.int32)
+        lora = self._lora_rows(list(plan.seq_ids), [len(sl) for sl in plan.prefill_slots])
         return ForwardBatch(
+            lora_idx=None if lora is None else _to_dev(lora, dev),
             input_ids=torch.tensor(ids, **i32).to(dev, non_blocking=True),
             positions=torch.tensor(pos, **i32).to(dev, non_blocking=True),
             slots=torch.tensor(slots, **i32).to(dev, non_blocking=True), is_prefill=True,
@@ -202,6 +223,9 @@ class ModelRunner:
                           logits_idx=torch.tensor(rows, dtype=torch.int64).to(dev, non_blocking=True),
                           num_decode=nd, prefix_lens=prefix if any(prefix) else None, prefix_cu=pre_cu,
                           prefix_tables=pre_tab)
+        lora = self._lora_rows(sids, [1] * nd + lens)
+        if lora is not None:
+            fb.lora_idx = _to_dev(lora, dev)
         # continuation chunks first, fresh prompts after them (the scheduler's order when it
         # resumes a partly prefilled prompt): only the continuations need the paged pass
         s1 = next((j for j, p in enumerate(prefix) if p == 0), len(prefix))
@@ -215,17 +239,22 @@ class ModelRunner:
         B = len(plan.seq_ids)
         self.kv.manager.fill_decode_tables(list(plan.seq_ids), self._tables_host[:B], self._ctx_host[:B])
         ids = last_tokens if isinstance(last_tokens, torch.Tensor) else np.asarray(last_tokens, dtype=np.int32)
-        return dict(ids=ids,
-                    pos=np.asarray(plan.decode_positions, dtype=np.int32),
-                    slots=np.asarray(plan.decode_slots, dtype=np.int32),
-                    tables=self._tables_host[:B], ctx=self._ctx_host[:B])
+        inp = dict(ids=ids,
+                   pos=np.asarray(plan.decode_positions, dtype=np.int32),
+                   slots=np.asarray(plan.decode_slots, dtype=np.int32),
+                   tables=self._tables_host[:B], ctx=self._ctx_host[:B])
+        lora = self._lora_rows(list(plan.seq_ids))
+        if lora is not None:      # the key is there only on steps with adapter rows
+            inp["lora"] = lora
+        return inp
 
     def decode_batch(self, inp: dict, ep_tokens: int = 0) -> ForwardBatch:
         dev = self.device
         t = lambda a: _to_dev(a, dev)  # noqa: E731
         return ForwardBatch(input_ids=t(inp["ids"]), positions=t(inp["pos"]), slots=t(inp["slots"]),
                             is_prefill=False, block_tables=t(inp["tables"]), ctx_lens=t(inp["ctx"]),
-                            max_ctx=self.max_seq_len, logits_idx=None, ep_tokens=ep_tokens)
+                            max_ctx=self.max_seq_len, logits_idx=None, ep_tokens=ep_tokens,
+                            lora_idx=None if inp.get("lora") is None else t(inp["lora"]))
 
     # ------------------------------------------------------------------------------------
     def run(self, fb: ForwardBatch, hidden_in=None):
@@ -247,7 +276,10 @@ class ModelRunner:
         B = len(inp["ids"])
         need = max(B, ep_tokens)
         self.last_ids = None
+        lora = inp.get("lora") is not None
         if self.recv_fn is not None or self.instances > 1:
+            if lora:
+                raise RuntimeError("LoRA steps are not supported on pipeline stages")
             if need > self.buckets[-1]:
                 raise RuntimeError(f"pipeline decode of {need} rows exceeds the largest bucket {self.buckets[-1]}")
             return self._run_pipeline_decode(self.bucket_of(need), inp, hidden_in)
@@ -256,17 +288,18 @@ class ModelRunner:
             fb.ep_alltoall = ep_alltoall
             return self.run(fb, hidden_in)
         bucket = self.buckets[bisect.bisect_left(self.buckets, need)]
-        if bucket in self.eager_buckets:
+        eager = self.lora_eager if lora else self.eager_buckets
+        if bucket in eager:
             return self.run(self.decode_batch(inp, ep_tokens), hidden_in)
-        g = self.graphs.get(bucket)
+        g = (self.lora_graphs if lora else self.graphs).get(bucket)
         if g is None:
             try:
-                g = self._capture(bucket)
+                g = self._capture(bucket, lora=lora)
             except Exception as e:  # capture unsupported here (e.g. a collective): stay eager
                 import warnings
 
                 warnings.warn(f"hipGraph capture of decode bucket {bucket} failed ({e!r}); running eagerly")
-                self.eager_buckets.add(bucket)
+                eager.add(bucket)
                 _recover_from_capture(self.device)
                 return self.run(self.decode_batch(inp, ep_tokens), hidden_in)
         self._stage(g, inp, hidden_in)
@@ -372,6 +405,9 @@ class ModelRunner:
         ht[B:] = 0.0
         hs[:B] = 0 if sd is None else sd
         hs[B:] = 0
+        if g.lora_idx is not None:
+            h[g.off_l:g.off_l + B] = inp["lora"]
+            h[g.off_l + B:g.off_l + b] = -1
         start = b if ids_dev else 0
         g.inbuf[start:].copy_(g.host[k][start:], non_blocking=True)
         if self.device.type == "cuda":
@@ -388,11 +424,11 @@ class ModelRunner:
     def _graph_batch(self, g: _DecodeGraph) -> ForwardBatch:
         return ForwardBatch(input_ids=g.input_ids, positions=g.positions, slots=g.slots,
                             is_prefill=False, block_tables=g.block_tables, ctx_lens=g.ctx_lens,
-                            max_ctx=self.max_seq_len, logits_idx=None, ep_tokens=g.bucket)
+                            max_ctx=self.max_seq_len, logits_idx=None, ep_tokens=g.bucket, lora_idx=g.lora_idx)
 
-    def _capture(self, bucket: int, register: bool = True) -> _DecodeGraph:
+    def _capture(self, bucket: int, register: bool = True, lora: bool = False) -> _DecodeGraph:
         m = self.model
-        g = _DecodeGraph(bucket, self.max_blocks, self.device, m.cfg.hidden_size, m.first)
+        g = _DecodeGraph(bucket, self.max_blocks, self.device, m.cfg.hidden_size, m.first, lora)
         fb = self._graph_batch(g)
         s = torch.cuda.Stream(self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
@@ -415,17 +451,18 @@ class ModelRunner:
                 g.ids = sample(g.output, g.temps, g.seeds)
         g.graph = graph
         if register:
-            self.graphs[bucket] = g
+            (self.lora_graphs if lora else self.graphs)[bucket] = g
         return g
 
     def close(self) -> None:
         """Drop every captured graph and the graph memory pool (before the communicators whose
         kernels the graphs captured are torn down: parallel/rccl.py)."""
-        for v in self.graphs.values():
+        for v in list(self.graphs.values()) + list(self.lora_graphs.values()):
             for g in (v if isinstance(v, list) else [v]):
                 g.graph = None
                 g.send_done = None
         self.graphs.clear()
+        self.lora_graphs.clear()
         self.last_instance = None
         self.pool = None
         import gc

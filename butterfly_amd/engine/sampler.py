@@ -40,6 +40,7 @@ class SamplingParams:
     presence_penalty: float = 0.0     # -2..2, subtracted once from every token generated so far
     frequency_penalty: float = 0.0    # -2..2, subtracted per occurrence among the generated tokens
     repetition_penalty: float = 1.0   # > 0, scales the logits of prompt and generated tokens
+    lora: Optional[str] = None        # name of a loaded LoRA adapter (LLMEngine.load_lora); None = base model
 
     @property
     def needs_filter(self) -> bool:

@@ -20,7 +20,8 @@ replayed (cli.py `generate`).
 Format `butterfly-engine-state` v1 (JSON): {"format", "version", "model", "job", "dp_rank", "dp_size",
 "next_id", "steps_done", "requests": [{"rid", "prompt", "output", "params", "finished",
 "finish_reason"}]}. `params` may lack fields added later (`logprobs`, the three penalties:
-absent = off; a resumed request's penalties see `prompt` as the prompt and `output` as generated); the
+absent = off; a resumed request's penalties see `prompt` as the prompt and `output` as generated; `lora`:
+the adapter's name, which the restoring engine must have loaded under the same name, else ValueError); the
 log-probabilities themselves are not stored, so tokens generated before the snapshot report None
 after a resume. Tokens still in flight in the asynchronous pipeline (sampled, value not yet
 on the host) are not part of it: they are recomputed after the resume.
@@ -86,6 +87,8 @@ def restore(engine, state: dict, job: Optional[str] = None) -> list:
         params = SamplingParams(**r["params"])
         prompt, output = list(r["prompt"]), list(r["output"])
         done = bool(r["finished"]) or len(output) >= params.max_tokens
+        if not done:
+            engine._resolve_lora(params)      # the adapter it names must be loaded here (ValueError)
         if not output and not done:
             engine.add_request(prompt, params, rid=rid)        # never started: the normal path
         else:

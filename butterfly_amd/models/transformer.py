@@ -102,6 +102,14 @@ class TransformerLM:
         # holds the e4m3 codes
         self.wscale: dict[str, torch.Tensor] = {}
         self.weight_dtype = "bf16"
+        # LoRA tables (enable_lora): stacked adapter slots per projection; _lora_idx is the
+        # adapter of every row of the step being run (forward), None for a plain step
+        self.lora_a: dict[str, torch.Tensor] = {}
+        self.lora_b: dict[str, torch.Tensor] = {}
+        self.lora_seg: dict[str, torch.Tensor] = {}
+        self.lora_scale: Optional[torch.Tensor] = None
+        self.lora_slots = self.lora_rank = self.lora_max_rank = 0
+        self._lora_idx: Optional[torch.Tensor] = None
         self._alloc()
         self.cos = self.sin = None
         if cfg.pos_emb == "rope":
@@ -274,6 +282,143 @@ class TransformerLM:
         per_byte = 2 if self.weight_dtype == "mxfp4" else 1
         return sorted({(self.p[k].shape[0], self.p[k].shape[1] * per_byte) for k in self.wscale})
 
+    # ------------------------------------------------------------------------------------
+    # LoRA adapters
+    # ------------------------------------------------------------------------------------
+    LORA_TARGETS = ("attn.q_proj", "attn.k_proj", "attn.v_proj", "attn.o_proj",
+                    "mlp.gate_proj", "mlp.up_proj", "mlp.down_proj")
+
+    def _lora_layout(self) -> dict:
+        """kind -> (N_local, K_local, nseg) of the four dense projections."""
+        c, d = self.cfg, self.dims
+        h, D = c.hidden_size, c.head_dim
+        return {"qkv_w": ((d.hq + 2 * d.hkv) * D, h, 3), "o_w": (h, d.hq * D, 1),
+                "gu_w": (2 * d.ffn, h, 2), "down_w": (h, d.ffn, 1)}
+
+    def enable_lora(self, max_loras: int, max_rank: int = 16) -> int:
+        """Allocate the adapter tables once, zeroed, at fixed addresses: per local layer and
+        projection a [S, J, K_local] and b [S, N_local, R] in the model dtype, one seg [N_local]
+        per projection kind and one scale [S] f32. S = max_loras slots of rank R, the smallest of
+        8 / 16 / 32 / 64 that holds max_rank; J = nseg * R with one rank slice per logical
+        projection fused in the weight (q | k | v, gate | up). Loading an adapter later is a copy
+        into a slot, so captured graphs stay valid. A forward pass uses the tables only when its
+        ForwardBatch carries `lora_idx`. Returns the bytes allocated."""
+        c = self.cfg
+        if c.is_moe:
+            raise ValueError("LoRA: MoE models are not supported (adapters target the dense projections)")
+        if c.bias:
+            raise ValueError("LoRA: models with linear biases are not supported")
+        if c.act != "silu":
+            raise ValueError("LoRA: only SwiGLU models are supported")
+        if int(max_loras) < 1:
+            raise ValueError(f"LoRA: max_loras must be at least 1 (got {max_loras})")
+        ranks = [r for r in ops.LORA_RANKS if r >= int(max_rank)]
+        if int(max_rank) < 1 or not ranks:
+            raise ValueError(f"LoRA: max_rank {max_rank} outside 1 .. {ops.LORA_RANKS[-1]}")
+        if self.lora_a:
+            raise ValueError("LoRA: the tables are already allocated")
+        S, R = int(max_loras), ranks[0]
+        layout = self._lora_layout()
+        if self.device.type == "cuda" and ops.load_library():
+            for kind, (N, K, nseg) in layout.items():
+                if torch.ops.bfly.lora_check(K, nseg * R, N, R) != 0:
+                    raise ValueError(f"LoRA: {kind} has a local shape [{N}, {K}] the kernels do not take "
+                                     "(K % 32, N % 16)")
+        z = lambda *s: torch.zeros(*s, dtype=self.dtype, device=self.device)  # noqa: E731
+        for i in self.layer_ids:
+            for kind, (N, K, nseg) in layout.items():
+                self.lora_a[f"l{i}.{kind}"] = z(S, nseg * R, K)
+                self.lora_b[f"l{i}.{kind}"] = z(S, N, R)
+        d, D = self.dims, c.head_dim
+        n = {k: torch.arange(v[0]) for k, v in layout.items()}
+        nq, nkv = d.hq * D, d.hkv * D
+        seg = {"qkv_w": (n["qkv_w"] >= nq).long() + (n["qkv_w"] >= nq + nkv).long(),
+               "gu_w": (n["gu_w"] // G16) % 2, "o_w": n["o_w"] * 0, "down_w": n["down_w"] * 0}
+        self.lora_seg = {k: v.to(torch.uint8).to(self.device) for k, v in seg.items()}
+        self.lora_scale = torch.zeros(S, dtype=torch.float32, device=self.device)
+        self.lora_slots, self.lora_rank, self.lora_max_rank = S, R, int(max_rank)
+        return self.lora_bytes()
+
+    def lora_bytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in list(self.lora_a.values()) + list(self.lora_b.values()))
+
+    def lora_max_j(self) -> int:
+        return 3 * self.lora_rank
+
+    def clear_lora(self, slot: int) -> None:
+        """Zero one slot: rows that still name it get a zero delta."""
+        self._lora_slot(slot)
+        for t in list(self.lora_a.values()) + list(self.lora_b.values()):
+            t[slot].zero_()
+        self.lora_scale[slot] = 0.0
+
+    def _lora_slot(self, slot: int) -> None:
+        if not self.lora_a:
+            raise ValueError("LoRA: enable_lora() has not been called")
+        if not 0 <= int(slot) < self.lora_slots:
+            raise ValueError(f"LoRA: slot {slot} outside 0 .. {self.lora_slots - 1}")
+
+    @torch.no_grad()
+    def load_lora(self, slot: int, tensors: dict, scale: float) -> None:
+        """Copy an adapter into a slot. `tensors`: logical (global-shape) tensors named like the
+        checkpoint's weights, layers.{i}.{attn.{q,k,v,o}_proj | mlp.{gate,up,down}_proj}.lora_A
+        [r, K] and .lora_B [N, r]; this rank takes the row / column slices logical_params() takes
+        of the weights (column-parallel: rows of B, A whole; row-parallel: columns of A, B whole).
+        Rank is padded with zeros to the slot rank; an absent target stays zero. The copies run on
+        the current stream, behind the steps already issued."""
+        self._lora_slot(slot)
+        c, d = self.cfg, self.dims
+        h, D, R = c.hidden_size, c.head_dim, self.lora_rank
+        nq, nkv, F = d.hq * D, d.hkv * D, d.ffn
+        # target -> (kind, rank slice, global N, global K, split ("rows" of B | "cols" of A), offset, length)
+        plan = {"attn.q_proj": ("qkv_w", 0, c.q_size, h, "rows", d.q_head0 * D, nq),
+                "attn.k_proj": ("qkv_w", 1, c.kv_size, h, "rows", d.kv_head0 * D, nkv),
+                "attn.v_proj": ("qkv_w", 2, c.kv_size, h, "rows", d.kv_head0 * D, nkv),
+                "attn.o_proj": ("o_w", 0, h, c.q_size, "cols", d.q_head0 * D, nq),
+                "mlp.gate_proj": ("gu_w", 0, c.intermediate_size, h, "rows", d.ffn0, F),
+                "mlp.up_proj": ("gu_w", 1, c.intermediate_size, h, "rows", d.ffn0, F),
+                "mlp.down_proj": ("down_w", 0, h, c.intermediate_size, "cols", d.ffn0, F)}
+        brow0 = {"attn.q_proj": 0, "attn.k_proj": nq, "attn.v_proj": nq + nkv}
+        known = {f"layers.{i}.{t}.lora_{m}" for i in range(c.num_layers) for t in plan for m in "AB"}
+        unknown = sorted(set(tensors) - known)
+        if unknown:
+            raise ValueError(f"LoRA: unknown adapter tensor {unknown[0]!r} (targets: the q / k / v / o / gate / up / "
+                             f"down projections of layers 0 .. {c.num_layers - 1})")
+        todo = []
+        for i in range(c.num_layers):
+            for t, (kind, sg, gN, gK, split, off, length) in plan.items():
+                A, B = tensors.get(f"layers.{i}.{t}.lora_A"), tensors.get(f"layers.{i}.{t}.lora_B")
+                if A is None and B is None:
+                    continue
+                if A is None or B is None:
+                    raise ValueError(f"LoRA: layers.{i}.{t} needs both lora_A and lora_B")
+                if A.dim() != 2 or B.dim() != 2 or A.shape[1] != gK or B.shape[0] != gN or A.shape[0] != B.shape[1]:
+                    raise ValueError(f"LoRA: layers.{i}.{t} has lora_A {tuple(A.shape)} / lora_B {tuple(B.shape)}, the "
+                                     f"base model needs [r, {gK}] / [{gN}, r]")
+                if A.shape[0] > self.lora_max_rank:
+                    raise ValueError(f"LoRA: layers.{i}.{t} has rank {A.shape[0]}, above max_rank {self.lora_max_rank}")
+                if i in self.layer_ids:
+                    todo.append((i, t, kind, sg, split, off, length, A, B))
+        for name in self.lora_a:
+            self.lora_a[name][slot].zero_()
+            self.lora_b[name][slot].zero_()
+        conv = dict(device=self.device, dtype=self.dtype)
+        for i, t, kind, sg, split, off, length, A, B in todo:
+            r = A.shape[0]
+            a, b = self.lora_a[f"l{i}.{kind}"][slot], self.lora_b[f"l{i}.{kind}"][slot]
+            if split == "cols":
+                a[:r].copy_(A[:, off:off + length].to(**conv))
+                b[:, :r].copy_(B.to(**conv))
+                continue
+            a[sg * R:sg * R + r].copy_(A.to(**conv))
+            Bl = torch.zeros(length, R, **conv)
+            Bl[:, :r].copy_(B[off:off + length].to(**conv))
+            if kind == "gu_w":
+                self._gu_getset(b, sg)[1](Bl)
+            else:
+                b[brow0[t]:brow0[t] + length].copy_(Bl)
+        self.lora_scale[slot] = float(scale)
+
     def logical_params(self) -> list[LogicalParam]:
         """Every logical (HF-style) parameter slice this rank holds."""
         if self.wscale:
@@ -429,8 +574,23 @@ class TransformerLM:
     def forward(self, fb: ForwardBatch, kv_caches: Optional[list] = None,
                 hidden_in: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Run this stage. Returns logits [R, vocab_local] on the last stage, else the
-        residual stream [T, hidden] to send to the next stage."""
-        if (self.seq_parallel and fb.is_prefill and fb.cp is None
+        residual stream [T, hidden] to send to the next stage. With `fb.lora_idx` the step adds
+        each row's adapter to the four dense projections and takes the plain-output route: no
+        deferred split-K reduce, no row-scale norm, no SwiGLU epilogue, no sequence parallelism."""
+        if fb.lora_idx is None:
+            return self._forward(fb, kv_caches, hidden_in)
+        if not self.lora_a:
+            raise ValueError("LoRA: the batch names adapters but enable_lora() has not been called")
+        if fb.cp is not None:
+            raise ValueError("LoRA: context-parallel prefill with adapters is not supported")
+        self._lora_idx = fb.lora_idx
+        try:
+            return self._forward(fb, kv_caches, hidden_in)
+        finally:
+            self._lora_idx = None
+
+    def _forward(self, fb: ForwardBatch, kv_caches: Optional[list], hidden_in: Optional[torch.Tensor]) -> torch.Tensor:
+        if (self.seq_parallel and fb.is_prefill and fb.cp is None and self._lora_idx is None
                 and fb.num_tokens >= max(self.sp_min_tokens, self.tp)):
             return self._forward_sp(fb, kv_caches, hidden_in)
         residual = self.embed(fb) if self.first else hidden_in
@@ -485,7 +645,18 @@ class TransformerLM:
     def _proj(self, name: str, x, epilogue: str = "none", bias=None, defer: bool = False):
         """One of the four dense projections (qkv / o / gate-up / down) of a layer: the FP8 or
         MXFP4 GEMM on its codes and scales when the weight is quantised (plain bf16 output, no
-        bias), else ops.linear on the bf16 weight and its packed copy."""
+        bias), else ops.linear on the bf16 weight and its packed copy. In a LoRA step: the base
+        GEMM with a plain tensor result, rounded to the model dtype, then the rows' adapter
+        deltas added in place (ops.lora_add_), then SwiGLU for gate/up."""
+        if self._lora_idx is not None:
+            if name in self.wscale:
+                linear_q = ops.linear_w4 if self.weight_dtype == "mxfp4" else ops.linear_w8
+                y = linear_q(x, self.p[name], self.wscale[name])
+            else:
+                y = ops.linear(x, self.p[name], packed=self.packed.get(name))
+            ops.lora_add_(y, x, self.lora_a[name], self.lora_b[name], self.lora_seg[name.split(".", 1)[1]],
+                          self.lora_scale, self._lora_idx)
+            return ops.silu_mul(y, interleave=G16) if epilogue == "silu" else y
         if name in self.wscale:
             linear_q = ops.linear_w4 if self.weight_dtype == "mxfp4" else ops.linear_w8
             return linear_q(x, self.p[name], self.wscale[name], epilogue=epilogue)
@@ -622,7 +793,8 @@ class TransformerLM:
         `consumer` (weight name, epilogue): the GEMM that reads the result; on decode-sized
         batches whose plan takes a row scale, the norm returns an `ops.RowNormed`."""
         w, b = self.p[prefix + "_w"], self.p.get(prefix + "_b")
-        if consumer is not None and not partial and 0 < residual.shape[0] <= self.rowscale_rows:
+        if (consumer is not None and not partial and 0 < residual.shape[0] <= self.rowscale_rows
+                and self._lora_idx is None):
             cw = self.p[consumer[0]]
             if ops.rowscale_ok(residual.shape[0], cw.shape[0], cw.shape[1], consumer[1]):
                 return ops.rms_norm(t, w, self.cfg.norm_eps, residual=residual, rows=True)

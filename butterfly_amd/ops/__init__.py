@@ -765,6 +765,66 @@ def linear_w4(x, code, scale, epilogue: str = "none", out=None):
     return linear(x, wd, epilogue=epilogue, out=out)
 
 
+LORA_RANKS = ref.LORA_RANKS
+LORA_MAX_SPLITK = 16     # kLoraMaxSplitK
+
+
+def _lora_part(x, J: int, splitk, arena: bool):
+    T, K = x.shape
+    ks = int(splitk) if splitk else torch.ops.bfly.lora_splitk(T, K)
+    n = ks * T * J
+    if arena:
+        part = _arena.get(x.device, "lora_t", n, torch.float32)[:n]
+        return (_poisoned(part) if _POISON else part).view(ks, T, J)
+    # stand-alone result: rows without an adapter are not written
+    return torch.zeros(ks, T, J, dtype=torch.float32, device=x.device)
+
+
+def lora_shrink(x, a, idx, splitk: int = 0):
+    """t [T, J] f32 = the rows' adapters' `a` times x (lora.hip; semantics in
+    ops.reference.lora_shrink): x [T, K], a [S, J, K], idx [T] int32, an index outside [0, S)
+    meaning no adapter (a zero row). `splitk`: the kernel's K split (0: its own choice); the
+    partial sums are added here in split order. The hot path is `lora_add_`."""
+    if not _gpu(x):
+        return ref.lora_shrink(x, a, idx)
+    part = _lora_part(x, a.shape[1], splitk, arena=False)
+    torch.ops.bfly.lora_shrink(x, a, idx, part)
+    t = part[0]
+    for k in range(1, part.shape[0]):
+        t = t + part[k]
+    return t
+
+
+def lora_expand_(y, t, b, seg, scale, idx):
+    """In place: y [T, N] += scale[s] * (t [T, J] f32 times b [S, N, R] of the rows' adapters),
+    seg [N] uint8 naming the rank slice of each output row, rows without an adapter untouched
+    (lora.hip; semantics in ops.reference.lora_expand_)."""
+    if not _gpu(y):
+        return ref.lora_expand_(y, t, b, seg, scale, idx)
+    torch.ops.bfly.lora_expand(y, t.view(1, *t.shape), b, seg, scale, idx)
+    return y
+
+
+def lora_add_(y, x, a, b, seg, scale, idx, splitk: int = 0):
+    """y += the LoRA delta of x under each row's adapter: shrink into the arena's `lora_t` slab
+    (K-split partial sums, reduced by the expand kernel), then expand in place. Two launches, no
+    allocation once the arena holds the slab (`reserve_lora_workspace`)."""
+    if not _gpu(y):
+        return ref.lora_add_(y, x, a, b, seg, scale, idx)
+    part = _lora_part(x, a.shape[1], splitk, arena=True)
+    torch.ops.bfly.lora_shrink(x, a, idx, part)
+    torch.ops.bfly.lora_expand(y, part, b, seg, scale, idx)
+    return y
+
+
+def reserve_lora_workspace(device, max_tokens: int, max_j: int) -> None:
+    """Size the `lora_t` slab for up to `max_tokens` rows of `max_j` rank columns (before capture)."""
+    if load_library() and torch.device(device).type == "cuda":
+        # lora_splitk(T, K) <= min(16, 512 / tiles): split x rows stays below 8192 or is T itself
+        rows = max(max_tokens, min(LORA_MAX_SPLITK * max(max_tokens, 1), 8192))
+        _arena.get(device, "lora_t", rows * max_j, torch.float32)
+
+
 def linear_silu_gate(x, w, gates, e0: int, num_local: int, packed=None):
     """The dense MoE decode gate/up GEMM over the concatenated local experts: SwiGLU, then every
     expert's column block scaled by its routing weight gates[:, e0 + e] — `linear(x, w, 'silu')`

@@ -512,6 +512,45 @@ def linear_w4(x, code, scale, epilogue="none", out=None):
     return linear(x, dequantize_mxfp4(code, scale, torch.float32), None, epilogue, out)
 
 
+LORA_RANKS = (8, 16, 32, 64)      # slot ranks of the LoRA tables (lora.hip)
+
+
+def lora_shrink(x, a, idx):
+    """t [T, J] f32 of x [T, K], a [S, J, K], idx [T] int32: for a row with 0 <= idx[m] < S,
+    t[m, j] = sum_k float(x[m, k]) * float(a[idx[m], j, k]) accumulated in f32; every other row
+    (no adapter) is zero."""
+    T, S = x.shape[0], a.shape[0]
+    t = torch.zeros(T, a.shape[1], dtype=torch.float32, device=x.device)
+    ix = idx.to(torch.int64)
+    rows = ((ix >= 0) & (ix < S)).nonzero().view(-1)
+    if rows.numel():
+        t[rows] = torch.bmm(a[ix[rows]].float(), x[rows].float().unsqueeze(2)).squeeze(2)
+    return t
+
+
+def lora_expand_(y, t, b, seg, scale, idx):
+    """In place on y [T, N]: for a row with 0 <= idx[m] = s < S,
+      y[m, n] = dtype(float(y[m, n]) + scale[s] * sum_{r < R} t[m, seg[n] * R + r] * float(b[s, n, r]))
+    with t [T, J] f32, b [S, N, R], seg [N] uint8 (the rank slice of output row n, constant over
+    aligned groups of 16 rows: the kernel reads it once per group), scale [S] f32. One rounding.
+    Rows without an adapter are not written."""
+    S, N, R = b.shape
+    ix = idx.to(torch.int64)
+    rows = ((ix >= 0) & (ix < S)).nonzero().view(-1)
+    if rows.numel():
+        sl = ix[rows]
+        cols = seg.to(torch.int64).view(N, 1) * R + torch.arange(R, device=seg.device).view(1, R)   # [N, R]
+        tt = t[rows].float()[:, cols]                                # [rows, N, R]
+        d = (tt * b[sl].float()).sum(-1) * scale.float()[sl].view(-1, 1)
+        y[rows] = (y[rows].float() + d).to(y.dtype)
+    return y
+
+
+def lora_add_(y, x, a, b, seg, scale, idx):
+    """y += the LoRA delta of the rows' adapters: lora_expand_(y, lora_shrink(x, a, idx), ...)."""
+    return lora_expand_(y, lora_shrink(x, a, idx), b, seg, scale, idx)
+
+
 def attn_prefill(q, k, v, cu_seqlens, max_seqlen, scale, causal=True, out=None, cu_seqlens_k=None,
                  return_lse=False):
     """q [T, Hq, D], k/v [Tk, Hkv, D]; varlen sequences given by cu_seqlens (int32), keys by

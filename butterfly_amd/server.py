@@ -195,8 +195,12 @@ def create_app(loop: ServingLoop):
 
     @app.get("/v1/models")
     def models():
-        return {"object": "list", "data": [{"id": loop.llm.cfg.name, "object": "model",
-                                            "weight_dtype": getattr(loop.llm.engine, "weight_dtype", "bf16")}]}
+        base = loop.llm.cfg.name
+        data = [{"id": base, "object": "model", "weight_dtype": getattr(loop.llm.engine, "weight_dtype", "bf16")}]
+        # the loaded LoRA adapters, selected by a request's "model" field
+        for name, info in sorted(getattr(loop.llm.engine, "_lora_info", {}).items()):
+            data.append({"id": name, "object": "model", "parent": base, "lora_rank": info["rank"]})
+        return {"object": "list", "data": data}
 
     @app.get("/metrics", response_class=PlainTextResponse)
     def metrics():
@@ -225,6 +229,10 @@ def create_app(loop: ServingLoop):
                                 top_k=req.top_k, seed=req.seed, stop_token_ids=req.stop_token_ids,
                                 logprobs=req.logprobs, presence_penalty=req.presence_penalty,
                                 frequency_penalty=req.frequency_penalty, repetition_penalty=req.repetition_penalty)
+        # "model" naming a loaded adapter runs the request with it; any other value is the base model
+        if req.model is not None and req.model in getattr(loop.llm.engine, "loras", {}):
+            params.lora = req.model
+        served = params.lora or loop.llm.cfg.name
         try:
             params.check_penalties()
         except ValueError as e:
@@ -245,7 +253,7 @@ def create_app(loop: ServingLoop):
                     else:
                         chunk = {"index": 0, "token_ids": [], "text": "" if is_text else None,
                                  "finish_reason": val["finish_reason"]}
-                    ev = {"id": f"cmpl-{gid}", "object": "text_completion", "model": loop.llm.cfg.name,
+                    ev = {"id": f"cmpl-{gid}", "object": "text_completion", "model": served,
                           "choices": [chunk]}
                     yield f"data: {json.dumps(ev)}\n\n"
                 yield "data: [DONE]\n\n"
@@ -257,7 +265,7 @@ def create_app(loop: ServingLoop):
         choice = {"index": 0, "text": text, "token_ids": res["token_ids"], "finish_reason": res["finish_reason"]}
         if res.get("logprobs") is not None:
             choice["logprobs"] = logprobs_json(res["token_ids"], res["logprobs"], is_text)
-        return {"id": f"cmpl-{gid}", "object": "text_completion", "model": loop.llm.cfg.name,
+        return {"id": f"cmpl-{gid}", "object": "text_completion", "model": served,
                 "choices": [choice],
                 "usage": {"prompt_tokens": len(ids), "completion_tokens": len(res["token_ids"])},
                 "timing": {"ttft_s": res["ttft_s"], "e2e_s": res["e2e_s"]}}

@@ -110,6 +110,8 @@ define("BFLY_PACKED_KINDS", "gu_w,moe_gu_w,qkv_w,o_w", str, "projection kinds pa
 define("BFLY_WEIGHT_DTYPE", "bf16", str, "dense projection weights of engines whose EngineConfig.weight_dtype is "
        "'auto': bf16, fp8 (weight-only e4m3 codes with one f32 scale per output row, csrc/kernels/gemm_w8.hip) "
        "or mxfp4 (weight-only OCP MXFP4: e2m1 codes with one e8m0 scale per 32 elements, csrc/kernels/gemm_w4.hip)")
+define("BFLY_MAX_LORAS", 0, int, "LoRA adapter slots of engines whose EngineConfig.max_loras is None (0: LoRA off; "
+       "csrc/kernels/lora.hip)")
 define("BFLY_MOE_NORM_ROUTE", True, _bool, "MoE layers at tp = 1: the add+RMSNorm over the O projection's split-K "
        "slabs also routes the rows (0: separate moe_route launch)")
 define("BFLY_MOE_GATE_EPILOGUE", True, _bool, "dense MoE decode path: the routing weights applied in the gate/up "

@@ -771,6 +771,45 @@ void gemm_w4(const Tensor& x, const Tensor& code, const Tensor& scale, Tensor& o
               " (rc=", rc, ")");
 }
 
+// Multi-LoRA delta (lora.hip): part [KS, T, J] f32 takes the shrink's K-split partial sums, KS
+// being the caller's choice (lora_splitk: the one ops.lora_add_ takes).
+void lora_shrink(const Tensor& x, const Tensor& a, const Tensor& idx, Tensor& part) {
+  const Op op("lora_shrink", x, "x");
+  const Rows<bf16> xr = op.rows<bf16>(x, "x", {-1, -1}, kAlign16 | kLd8);
+  const int64_t T = x.size(0), K = x.size(1);
+  const bf16* ap = op.shaped<bf16>(a, "a", {-1, -1, K}, kAlign16);
+  const int64_t S = a.size(0), J = a.size(1);
+  TORCH_CHECK(K % 32 == 0 && K > 0 && K < (1LL << 31) && T < (1LL << 27), "lora_shrink: K % 32, shape");
+  TORCH_CHECK(S >= 1 && S < (1LL << 20) && J >= 8 && J % 8 == 0 && J <= 192, "lora_shrink: a [S >= 1, J = 8 .. 192 (J % 8), K]");
+  const int* ip = op.flat<int>(idx, "idx", T);
+  float* pp = op.shaped<float>(part, "part", {-1, T, J}, kAlign16);
+  const int64_t KS = part.size(0);
+  TORCH_CHECK(KS >= 1 && KS <= bfly::kLoraMaxSplitK, "lora_shrink: part [KS = 1 .. ", bfly::kLoraMaxSplitK, ", T, J]");
+  auto g = op.guard();
+  bfly::launch_lora_shrink(xr.p, xr.ld, ap, ip, pp, (int)KS, (int)T, (int)K, (int)J, (int)S, cur_stream());
+}
+
+void lora_expand(Tensor& y, const Tensor& part, const Tensor& b, const Tensor& seg, const Tensor& scale,
+                 const Tensor& idx) {
+  const Op op("lora_expand", y, "y");
+  const Rows<bf16> yr = op.rows<bf16>(y, "y", {-1, -1}, kAlign8 | kLd4);
+  const int64_t T = y.size(0), N = y.size(1);
+  const float* pp = op.shaped<float>(part, "part", {-1, T, -1}, kAlign16);
+  const int64_t KS = part.size(0), J = part.size(2);
+  const bf16* bp = op.shaped<bf16>(b, "b", {-1, N, -1}, kAlign16);
+  const int64_t S = b.size(0), R = b.size(2);
+  TORCH_CHECK(N < (1LL << 31) && T < (1LL << 27) && bfly::lora_check(32, (int)J, (int)N, (int)R) == 0,
+              "lora_expand: N % 16, R of 8 / 16 / 32 / 64, J = nseg R with nseg 1 .. 3; got N=", N, " R=", R, " J=", J);
+  TORCH_CHECK(S >= 1 && S < (1LL << 20) && KS >= 1 && KS <= bfly::kLoraMaxSplitK, "lora_expand: b [S >= 1, N, R], part [KS = 1 .. ",
+              bfly::kLoraMaxSplitK, ", T, J]");
+  const uint8_t* sp = op.shaped<uint8_t>(seg, "seg", {N});
+  const float* cp = op.shaped<float>(scale, "scale", {S});
+  const int* ip = op.flat<int>(idx, "idx", T);
+  auto g = op.guard();
+  bfly::launch_lora_expand(yr.p, yr.ld, pp, (int)KS, (int)T, (int)J, bp, (int)N, (int)R, sp, cp, ip, (int)S,
+                           cur_stream());
+}
+
 // 0 when the plan for (M, N, K, epilogue) has a packed-weight form
 int64_t gemm_packed_check(int64_t M, int64_t N, int64_t K, int64_t epilogue) {
   return bfly::gemm_packed_check((int)M, (int)N, (int)K, (int)epilogue);
@@ -1307,6 +1346,11 @@ TORCH_LIBRARY(bfly, m) {
         [](int64_t M, int64_t N, int64_t K, int64_t e) -> int64_t { return bfly::gemm_w4_splitk(M, N, K, e); });
   m.def("gemm_w4_workspace_size(int M, int N, int K) -> int",
         [](int64_t M, int64_t N, int64_t K) -> int64_t { return (int64_t)bfly::gemm_w4_workspace_bytes(M, N, K); });
+  m.def("lora_shrink(Tensor x, Tensor a, Tensor idx, Tensor(a!) part) -> ()", &lora_shrink);
+  m.def("lora_expand(Tensor(a!) y, Tensor part, Tensor b, Tensor seg, Tensor scale, Tensor idx) -> ()", &lora_expand);
+  m.def("lora_splitk(int T, int K) -> int", [](int64_t T, int64_t K) -> int64_t { return bfly::lora_splitk((int)T, (int)K); });
+  m.def("lora_check(int K, int J, int N, int R) -> int",
+        [](int64_t K, int64_t J, int64_t N, int64_t R) -> int64_t { return bfly::lora_check((int)K, (int)J, (int)N, (int)R); });
   m.def("gemm_with_plan(Tensor x, Tensor w, Tensor(a!) out, int[] plan, int epilogue, Tensor(b!)? workspace, "
         "Tensor? bias=None, bool packed=False) -> ()");
   m.def("gemm_plan_check(int[] plan, int M, int N, int K, int epilogue, bool packed=False) -> int", &gemm_plan_check);

@@ -151,6 +151,20 @@ void launch_apply_penalties(const bf16* logits, long row_stride, int rows, int V
                             const int* lens, const int* prompt_lens, const int* last,
                             const float* params, bf16* out, long out_stride, hipStream_t stream);
 
+// lora.hip: per-row LoRA delta of a projection's bf16 output. x [T][K] rows (ldx), a [S][J][K],
+// b [S][N][R] bf16, J = nseg * R (nseg 1..3 logical projections fused in the weight), seg [N]
+// uint8 (the rank slice of output row n, read once per aligned 16 rows and cut to nseg - 1),
+// scale [S] f32, idx [T] int32 (outside [0, S): no adapter, the row of y is not written).
+// part [KS][T][J] f32 holds the shrink's K-split partial sums; rows without an adapter are not
+// written there and not read by the expand.
+constexpr int kLoraMaxSplitK = 16;
+int lora_splitk(int T, int K);                  // the K split ops.lora_add_ uses (any 1..16 runs)
+int lora_check(int K, int J, int N, int R);     // 0, or < 0: K % 32, N % 16, R of 8 / 16 / 32 / 64, J = 1..3 R
+void launch_lora_shrink(const bf16* x, long ldx, const bf16* a, const int* idx, float* part, int KS, int T,
+                        int K, int J, int S, hipStream_t stream);
+void launch_lora_expand(bf16* y, long ldy, const float* part, int KS, int T, int J, const bf16* b, int N, int R,
+                        const uint8_t* seg, const float* scale, const int* idx, int S, hipStream_t stream);
+
 // gemm.hip
 GemmPlan plan_gemm(int M, int N, int K);
 size_t gemm_workspace_bytes(int M, int N, int K);
