@@ -1,4 +1,4 @@
-"""HuggingFace checkpoint import: Llama / Mistral / Mixtral / GPT-2 safetensors -> butterfly-ckpt.
+"""HuggingFace checkpoint import: Llama / Mistral / Mixtral / Qwen3 / GPT-2 safetensors -> butterfly-ckpt.
 
 Maps HF parameter names to our logical names (the names `TransformerLM.logical_params()`
 uses) and converts layouts (GPT-2's Conv1D weights are stored [in, out] and its attention is
@@ -27,6 +27,7 @@ _LLAMA = [
     (r"model\.layers\.(\d+)\.input_layernorm\.weight", r"layers.\1.input_norm.weight"),
     (r"model\.layers\.(\d+)\.post_attention_layernorm\.weight", r"layers.\1.post_norm.weight"),
     (r"model\.layers\.(\d+)\.self_attn\.(q|k|v|o)_proj\.weight", r"layers.\1.attn.\2_proj.weight"),
+    (r"model\.layers\.(\d+)\.self_attn\.(q|k)_norm\.weight", r"layers.\1.attn.\2_norm.weight"),
     (r"model\.layers\.(\d+)\.mlp\.(gate|up|down)_proj\.weight", r"layers.\1.mlp.\2_proj.weight"),
     (r"model\.layers\.(\d+)\.block_sparse_moe\.gate\.weight", r"layers.\1.moe.router.weight"),
     (r"model\.layers\.(\d+)\.block_sparse_moe\.experts\.(\d+)\.w1\.weight", r"layers.\1.moe.experts.\2.gate_proj.weight"),
@@ -124,7 +125,10 @@ def convert_hf(src: str | Path, dst: str | Path, dtype: torch.dtype = torch.bflo
             for k in fh.keys():
                 t = fh.get_tensor(k)
                 it = _gpt2_map(k, t, cfg.hidden_size) if cfg.arch == "gpt2" else _llama_map(k, t)
-                for ln, tt in it:
+                mapped = list(it)
+                if cfg.qk_norm and not mapped:
+                    raise ValueError(f"{f.name}: tensor {k!r} has no place in a {hf_cfg.get('model_type')} model")
+                for ln, tt in mapped:
                     if ln == "lm_head.weight" and cfg.tie_embeddings:
                         continue
                     out[ln] = tt.to(dtype).contiguous()

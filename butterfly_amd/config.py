@@ -36,6 +36,7 @@ class ModelConfig:
     num_experts: int = 0            # > 0: MoE FFN
     experts_per_token: int = 0
     init_std: float = 0.02
+    qk_norm: bool = False           # per-head RMSNorm of Q and K in front of RoPE (Qwen3)
 
     # ---- derived quantities ------------------------------------------------------------
     @property
@@ -60,6 +61,8 @@ class ModelConfig:
         if self.is_moe:
             mlp = mlp * self.num_experts + h * self.num_experts
         norms = 2 * h * (2 if self.norm == "layer" else 1)
+        if self.qk_norm:
+            norms += 2 * self.head_dim
         b = 0
         if self.bias:
             b = self.q_size + 2 * self.kv_size + h + f + h
@@ -102,7 +105,7 @@ class ModelConfig:
 
     @classmethod
     def from_hf(cls, hf: dict, name: str = "hf") -> "ModelConfig":
-        """Map a HuggingFace config.json (Llama / Mistral / Mixtral / GPT-2) to ModelConfig."""
+        """Map a HuggingFace config.json (Llama / Mistral / Mixtral / Qwen3 / GPT-2) to ModelConfig."""
         mt = hf.get("model_type", "llama")
         if mt == "gpt2":
             h = hf["n_embd"]
@@ -114,6 +117,13 @@ class ModelConfig:
         h = hf["hidden_size"]
         nh = hf["num_attention_heads"]
         arch = "mixtral" if mt == "mixtral" else "llama"
+        # what the importer cannot represent is refused, not dropped: bias tensors have no
+        # place in the llama / mixtral layers, and every layer attends to the whole context
+        for key in ("attention_bias", "mlp_bias"):
+            if hf.get(key):
+                raise ValueError(f"{mt} config with {key}=true is not supported (its bias tensors would be dropped)")
+        if mt == "qwen3" and hf.get("use_sliding_window"):
+            raise ValueError("qwen3 config with use_sliding_window=true is not supported")
         # rope: older configs carry rope_theta / rope_scaling at top level, newer ones a
         # "rope_parameters" dict; llama3-style frequency scaling is normalised to our keys
         rp = dict(hf.get("rope_parameters") or {})
@@ -131,7 +141,8 @@ class ModelConfig:
                    norm_eps=hf.get("rms_norm_eps", 1e-5),
                    tie_embeddings=hf.get("tie_word_embeddings", False),
                    num_experts=hf.get("num_local_experts", 0),
-                   experts_per_token=hf.get("num_experts_per_tok", 0))
+                   experts_per_token=hf.get("num_experts_per_tok", 0),
+                   qk_norm=mt == "qwen3")
 
 
 PRESETS: dict[str, dict[str, Any]] = {
@@ -154,10 +165,20 @@ PRESETS: dict[str, dict[str, Any]] = {
     "mixtral-8x7b": dict(arch="mixtral", vocab_size=32000, hidden_size=4096, intermediate_size=14336,
                          num_layers=32, num_heads=32, num_kv_heads=8, head_dim=128,
                          max_position=32768, rope_theta=1e6, num_experts=8, experts_per_token=2),
+    # Qwen3 dense: the Llama layer plus a per-head RMSNorm of Q and K in front of RoPE
+    "qwen3-8b": dict(arch="llama", vocab_size=151936, hidden_size=4096, intermediate_size=12288,
+                     num_layers=36, num_heads=32, num_kv_heads=8, head_dim=128, max_position=40960,
+                     rope_theta=1e6, norm_eps=1e-6, qk_norm=True),
+    "qwen3-32b": dict(arch="llama", vocab_size=151936, hidden_size=5120, intermediate_size=25600,
+                      num_layers=64, num_heads=64, num_kv_heads=8, head_dim=128, max_position=40960,
+                      rope_theta=1e6, norm_eps=1e-6, qk_norm=True),
     # Small configs for tests (same code paths, GPU-kernel-compatible dims).
     "llama-tiny": dict(arch="llama", vocab_size=1024, hidden_size=256, intermediate_size=512,
                        num_layers=2, num_heads=4, num_kv_heads=2, head_dim=128, max_position=2048,
                        rope_theta=10000.0, init_std=0.05),
+    "qwen3-tiny": dict(arch="llama", vocab_size=1024, hidden_size=256, intermediate_size=512,
+                       num_layers=2, num_heads=4, num_kv_heads=2, head_dim=128, max_position=2048,
+                       rope_theta=10000.0, init_std=0.05, qk_norm=True),
     "llama-small": dict(arch="llama", vocab_size=4096, hidden_size=1024, intermediate_size=2048,
                         num_layers=4, num_heads=8, num_kv_heads=2, head_dim=128, max_position=4096,
                         rope_theta=500000.0, init_std=0.05),

@@ -89,7 +89,7 @@ class ModelIR:
 OP_KERNELS = {
     "embed": "embed_kernel", "norm": "rmsnorm_kernel | layernorm_kernel (fused residual add)",
     "gemm": "gemm_tile_kernel | gemm_skinny_kernel (+ split-K reduce)",
-    "rope": "rope_kv_kernel (fused KV-cache append) | kv_append_kernel",
+    "rope": "rope_kv_kernel (fused KV-cache append; QKNORM: per-head QK-norm first) | kv_append_kernel",
     "attn": "attn_decode_kernel + attn_decode_combine_kernel | attn_prefill_kernel",
     "act": "gemm SiLU epilogue | gelu_kernel", "route": "moe_route_kernel + moe_gate_scale_kernel",
     "collective": "allreduce_kernel (one-shot IPC, fused add+norm) | RCCL",
@@ -117,7 +117,9 @@ def build_ir(cfg: ModelConfig, tp: int = 1, ep: int = 1) -> ModelIR:
                           params=((L + "attn.qkv_proj.weight", (qkv_n, h)),)
                           + (((L + "attn.qkv_proj.bias", (qkv_n,)),) if cfg.bias else ())))
         if cfg.pos_emb == "rope":
-            ops.append(OpSpec("rope_kv", "rope", width=(hq + 2 * hkv) * D))
+            # Qwen3: the per-head QK-norm weights are read by the same kernel (whole on every rank)
+            qk = ((L + "attn.q_norm.weight", (D,)), (L + "attn.k_norm.weight", (D,))) if cfg.qk_norm else ()
+            ops.append(OpSpec("rope_kv", "rope", params=qk, width=(hq + 2 * hkv) * D))
         ops.append(OpSpec("attention", "attn", width=hq * D))
         ops.append(OpSpec("o", "gemm", n=h, k=hq * D,
                           params=((L + "attn.o_proj.weight", (h, hq * D)),)

@@ -93,6 +93,8 @@ class TransformerLM:
         self.rowscale_rows = (flags.get("BFLY_NORM_ROWSCALE_MAX_ROWS")
                               if (self.device.type == "cuda" and cfg.norm == "rms" and self.tp == 1
                                   and not cfg.is_moe and flags.get("BFLY_NORM_ROWSCALE")) else 0)
+        if cfg.qk_norm and (cfg.pos_emb != "rope" or cfg.norm != "rms"):
+            raise NotImplementedError("qk_norm is the per-head RMSNorm in front of RoPE: it needs pos_emb 'rope' and norm 'rms'")
         if self.device.type == "cuda" and cfg.head_dim != 128:
             raise NotImplementedError(f"GPU attention kernels need head_dim 128 (got {cfg.head_dim})")
         self.p: dict[str, torch.Tensor] = {}
@@ -138,6 +140,9 @@ class TransformerLM:
                 self.p[pre + "in_b"] = z(h)
             self.p[pre + "qkv_w"] = z((d.hq + 2 * d.hkv) * D, h)
             self.p[pre + "o_w"] = z(h, d.hq * D)
+            if c.qk_norm:   # one [head_dim] weight for all Q heads, one for all K heads: whole on every TP rank
+                self.p[pre + "q_norm_w"] = z(D)
+                self.p[pre + "k_norm_w"] = z(D)
             if c.bias:
                 self.p[pre + "qkv_b"] = z((d.hq + 2 * d.hkv) * D)
                 self.p[pre + "o_b"] = z(h)
@@ -464,6 +469,9 @@ class TransformerLM:
                 add(L + "attn.q_proj.bias", (c.q_size,), 0, d.q_head0 * D, nq, "normal", rows(qb, 0, nq), ep0)
                 add(L + "attn.k_proj.bias", (c.kv_size,), 0, d.kv_head0 * D, nkv, "normal", rows(qb, nq, nkv), kv_owner)
                 add(L + "attn.v_proj.bias", (c.kv_size,), 0, d.kv_head0 * D, nkv, "normal", rows(qb, nq + nkv, nkv), kv_owner)
+            if c.qk_norm:
+                add(L + "attn.q_norm.weight", (D,), None, 0, 0, "ones", whole(self.p[pre + "q_norm_w"]), tp0 and ep0)
+                add(L + "attn.k_norm.weight", (D,), None, 0, 0, "ones", whole(self.p[pre + "k_norm_w"]), tp0 and ep0)
             ow = self.p[pre + "o_w"]
             add(L + "attn.o_proj.weight", (h, c.q_size), 1, d.q_head0 * D, nq, "normal", whole(ow), ep0)
             if c.bias:
@@ -665,7 +673,8 @@ class TransformerLM:
 
     def _attention_block(self, li: int, pre: str, x: torch.Tensor, fb: ForwardBatch,
                          kv_caches: Optional[list]):
-        """normed x [T, h] -> QKV GEMM -> RoPE + KV append -> attention -> O GEMM (TP-partial)."""
+        """normed x [T, h] -> QKV GEMM -> (per-head QK-norm +) RoPE + KV append -> attention ->
+        O GEMM (TP-partial)."""
         c, d = self.cfg, self.dims
         T, D = fb.num_tokens, c.head_dim
         kc, vc = kv_caches[li] if kv_caches is not None else (None, None)
@@ -674,7 +683,9 @@ class TransformerLM:
         # when no all-reduce sits in between (tp == 1)
         qkv = self._proj(pre + "qkv_w", x, bias=self.p.get(pre + "qkv_b"), defer=self.defer_qkv)
         if c.pos_emb == "rope":
-            qkv = ops.rope_kv(qkv, fb.positions, self.cos, self.sin, d.hq, d.hkv, slots, kc, vc)
+            qkv = ops.rope_kv(qkv, fb.positions, self.cos, self.sin, d.hq, d.hkv, slots, kc, vc,
+                              q_norm=self.p.get(pre + "q_norm_w"), k_norm=self.p.get(pre + "k_norm_w"),
+                              eps=c.norm_eps)
         elif kc is not None:
             k3 = qkv[:, d.hq * D:(d.hq + d.hkv) * D].view(T, d.hkv, D)
             v3 = qkv[:, (d.hq + d.hkv) * D:].view(T, d.hkv, D)

@@ -349,9 +349,23 @@ def layer_norm(x, w, b, eps: float, out=None, residual=None):
 
 
 def rope_kv(qkv, positions, cos, sin, n_q: int, n_kv: int, slots=None, k_cache=None,
-            v_cache=None):
+            v_cache=None, q_norm=None, k_norm=None, eps: float = 0.0):
     """In-place RoPE on the Q/K heads of a fused QKV row; optional paged KV append. Returns the
-    (bf16) QKV rows; `qkv` may be a deferred split-K GEMM output whose reduce is fused here."""
+    (bf16) QKV rows; `qkv` may be a deferred split-K GEMM output whose reduce is fused here.
+    With `q_norm` / `k_norm` ([head_dim] weights, Qwen3) every Q / K head is RMS-normalised and
+    scaled in front of the rotation, in the same kernel (rope.hip, QKNORM)."""
+    if (q_norm is None) != (k_norm is None):
+        raise ValueError("rope_kv: q_norm and k_norm go together")
+    if q_norm is not None:
+        if isinstance(qkv, Partial):
+            torch.ops.bfly.rope_qknorm_kv(qkv.out, positions, cos, sin, n_q, n_kv, slots, k_cache, v_cache,
+                                          q_norm, k_norm, eps, qkv.slabs)
+            return qkv.out
+        if not _gpu(qkv):
+            return ref.rope_kv(qkv, positions, cos, sin, n_q, n_kv, slots, k_cache, v_cache, q_norm, k_norm, eps)
+        torch.ops.bfly.rope_qknorm_kv(qkv, positions, cos, sin, n_q, n_kv, slots, k_cache, v_cache,
+                                      q_norm, k_norm, eps)
+        return qkv
     if isinstance(qkv, Partial):
         torch.ops.bfly.rope_kv(qkv.out, positions, cos, sin, n_q, n_kv, slots, k_cache, v_cache, qkv.slabs)
         return qkv.out

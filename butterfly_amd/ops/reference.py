@@ -197,13 +197,22 @@ def gather_rows(src, idx, out):
     return out
 
 
-def rope_kv(qkv, positions, cos, sin, n_q, n_kv, slots=None, k_cache=None, v_cache=None):
+def rope_kv(qkv, positions, cos, sin, n_q, n_kv, slots=None, k_cache=None, v_cache=None,
+            q_norm=None, k_norm=None, eps=0.0):
+    """With `q_norm` / `k_norm` ([D] each, Qwen3): every Q / K head is RMS-normalised over its D
+    elements and scaled by the weight before the rotation, all in f32: x * rsqrt(mean(x^2) + eps)
+    * w, then the rotation, then one rounding to the dtype of `qkv`."""
     T = qkv.shape[0]
     D = qkv.shape[1] // (n_q + 2 * n_kv)
     v3 = qkv.view(T, n_q + 2 * n_kv, D)
     c = cos[positions.long()].unsqueeze(1)
     s = sin[positions.long()].unsqueeze(1)
-    rot = _rotate(v3[:, : n_q + n_kv], c, s).to(qkv.dtype)
+    x = v3[:, : n_q + n_kv]
+    if q_norm is not None or k_norm is not None:
+        x = x.float()
+        w = torch.cat([q_norm.float().expand(n_q, D), k_norm.float().expand(n_kv, D)], 0)
+        x = x * torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + eps) * w
+    rot = _rotate(x, c, s).to(qkv.dtype)
     v3[:, : n_q + n_kv] = rot
     if slots is not None:
         kv_append(v3[:, n_q: n_q + n_kv], v3[:, n_q + n_kv:], slots, k_cache, v_cache)

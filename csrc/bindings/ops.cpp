@@ -14,6 +14,8 @@
 #include <c10/core/DeviceGuard.h>
 #include <torch/library.h>
 
+#include <cmath>
+
 #include "bfly_kernels.h"
 
 namespace {
@@ -332,32 +334,60 @@ void layer_norm(const Tensor& x, const Tensor& w, const Tensor& b, double eps, T
                          op.shaped<bf16>(out, "out", {rows, dim}), rows, dim, (float)eps, res != nullptr, cur_stream());
 }
 
-void rope_kv(Tensor& qkv, const Tensor& positions, const Tensor& cos_t, const Tensor& sin_t,
-             int64_t num_q_heads, int64_t num_kv_heads, const OptTensor& slots, const OptTensor& k_cache,
-             const OptTensor& v_cache, const OptTensor& partial) {
-  const Op op("rope_kv", qkv, "qkv");
+// rope_kv and rope_qknorm_kv: with `q_norm_w` / `k_norm_w` (both or neither) the launch is the
+// variant that RMS-normalises every Q / K head in front of the rotation
+void rope_kv_any(const char* name, Tensor& qkv, const Tensor& positions, const Tensor& cos_t, const Tensor& sin_t,
+                 int64_t num_q_heads, int64_t num_kv_heads, const OptTensor& slots, const OptTensor& k_cache,
+                 const OptTensor& v_cache, const OptTensor& partial, const Tensor* q_norm_w, const Tensor* k_norm_w,
+                 double eps) {
+  const Op op(name, qkv, "qkv");
   bf16* qp = op.shaped<bf16>(qkv, "qkv", {-1, -1});
   const int T = qkv.size(0);
+  TORCH_CHECK(num_q_heads >= 0 && num_kv_heads >= 0, name, ": negative head count");
   const int H = num_q_heads + 2 * num_kv_heads;
-  TORCH_CHECK(H > 0 && qkv.size(1) % H == 0, "rope_kv: row length not divisible by heads");
+  TORCH_CHECK(H > 0 && qkv.size(1) % H == 0, name, ": row length not divisible by heads");
   const int D = qkv.size(1) / H;
-  TORCH_CHECK(D == 128 || D == 64, "rope_kv: head_dim must be 64 or 128");
+  TORCH_CHECK(D == 128 || D == 64, name, ": head_dim must be 64 or 128");
   const int* pos = op.flat<int>(positions, "positions", T);
   const float* cp = op.flat_min<float>(cos_t, "cos", 0);
-  TORCH_CHECK(cos_t.dim() >= 1 && cos_t.size(-1) == D / 2, "rope_kv: cos must be [max_pos, D/2]");
+  TORCH_CHECK(cos_t.dim() >= 1 && cos_t.size(-1) == D / 2, name, ": cos must be [max_pos, D/2]");
   const float* sp = op.flat<float>(sin_t, "sin", cos_t.numel());
-  TORCH_CHECK(sin_t.sizes() == cos_t.sizes(), "rope_kv: sin must have the shape of cos");
+  TORCH_CHECK(sin_t.sizes() == cos_t.sizes(), name, ": sin must have the shape of cos");
   const int* sl = op.flat<int>(slots, "slots", T);
   KvCaches kv{nullptr, nullptr, 0, 1, 0};
   if (slots.has_value()) {
-    TORCH_CHECK(k_cache.has_value() && v_cache.has_value(), "rope_kv: caches required with slots");
+    TORCH_CHECK(k_cache.has_value() && v_cache.has_value(), name, ": caches required with slots");
     kv = kv_caches(op, *k_cache, *v_cache, num_kv_heads, D);
   }
   Slabs part{nullptr, 0};
   if (partial.has_value()) part = slabs_of(op, *partial, "partial", T, qkv.size(1));
+  if (q_norm_w == nullptr) {
+    auto g = op.guard();
+    bfly::launch_rope_kv(qp, T, num_q_heads, num_kv_heads, D, pos, cp, sp, sl, kv.k, kv.v, kv.BS, cur_stream(),
+                         part.p, part.sk, kv.fp8);
+    return;
+  }
+  const bf16* qw = op.flat<bf16>(*q_norm_w, "q_norm_w", D, kAlign16);
+  const bf16* kw = op.flat<bf16>(*k_norm_w, "k_norm_w", D, kAlign16);
+  TORCH_CHECK(eps >= 0.0 && std::isfinite(eps), name, ": eps must be finite and >= 0");
   auto g = op.guard();
-  bfly::launch_rope_kv(qp, T, num_q_heads, num_kv_heads, D, pos, cp, sp, sl, kv.k, kv.v, kv.BS, cur_stream(),
-                       part.p, part.sk, kv.fp8);
+  bfly::launch_rope_qknorm_kv(qp, T, num_q_heads, num_kv_heads, D, pos, cp, sp, sl, kv.k, kv.v, kv.BS, cur_stream(),
+                              part.p, part.sk, kv.fp8, qw, kw, (float)eps);
+}
+
+void rope_kv(Tensor& qkv, const Tensor& positions, const Tensor& cos_t, const Tensor& sin_t,
+             int64_t num_q_heads, int64_t num_kv_heads, const OptTensor& slots, const OptTensor& k_cache,
+             const OptTensor& v_cache, const OptTensor& partial) {
+  rope_kv_any("rope_kv", qkv, positions, cos_t, sin_t, num_q_heads, num_kv_heads, slots, k_cache, v_cache, partial,
+              nullptr, nullptr, 0.0);
+}
+
+void rope_qknorm_kv(Tensor& qkv, const Tensor& positions, const Tensor& cos_t, const Tensor& sin_t,
+                    int64_t num_q_heads, int64_t num_kv_heads, const OptTensor& slots, const OptTensor& k_cache,
+                    const OptTensor& v_cache, const Tensor& q_norm_w, const Tensor& k_norm_w, double eps,
+                    const OptTensor& partial) {
+  rope_kv_any("rope_qknorm_kv", qkv, positions, cos_t, sin_t, num_q_heads, num_kv_heads, slots, k_cache, v_cache,
+              partial, &q_norm_w, &k_norm_w, eps);
 }
 
 void kv_append(const Tensor& k, const Tensor& v, const Tensor& slots, Tensor& k_cache, Tensor& v_cache) {
@@ -1346,6 +1376,9 @@ TORCH_LIBRARY(bfly, m) {
         [](int64_t M, int64_t N, int64_t K, int64_t e) -> int64_t { return bfly::gemm_w4_splitk(M, N, K, e); });
   m.def("gemm_w4_workspace_size(int M, int N, int K) -> int",
         [](int64_t M, int64_t N, int64_t K) -> int64_t { return (int64_t)bfly::gemm_w4_workspace_bytes(M, N, K); });
+  m.def("rope_qknorm_kv(Tensor(a!) qkv, Tensor positions, Tensor cos, Tensor sin, int num_q_heads, "
+        "int num_kv_heads, Tensor? slots, Tensor(b!)? k_cache, Tensor(c!)? v_cache, Tensor q_norm_w, Tensor k_norm_w, "
+        "float eps, Tensor? partial=None) -> ()", &rope_qknorm_kv);
   m.def("lora_shrink(Tensor x, Tensor a, Tensor idx, Tensor(a!) part) -> ()", &lora_shrink);
   m.def("lora_expand(Tensor(a!) y, Tensor part, Tensor b, Tensor seg, Tensor scale, Tensor idx) -> ()", &lora_expand);
   m.def("lora_splitk(int T, int K) -> int", [](int64_t T, int64_t K) -> int64_t { return bfly::lora_splitk((int)T, (int)K); });

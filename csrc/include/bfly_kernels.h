@@ -84,6 +84,12 @@ void launch_rope_kv(bf16* qkv, int T, int Hq, int Hkv, int D, const int* positio
                     const float* cos_t, const float* sin_t, const int* slots, void* k_cache,
                     void* v_cache, int block_size, hipStream_t stream,
                     const float* part = nullptr, int sk = 0, int kv_fp8 = 0);
+// launch_rope_kv with the per-head QK-norm of Qwen3 in front of the rotation: every Q / K head
+// times rsqrt(mean of its squares + eps) times `q_norm_w` / `k_norm_w` (bf16 [D] each)
+void launch_rope_qknorm_kv(bf16* qkv, int T, int Hq, int Hkv, int D, const int* positions,
+                           const float* cos_t, const float* sin_t, const int* slots, void* k_cache,
+                           void* v_cache, int block_size, hipStream_t stream, const float* part, int sk,
+                           int kv_fp8, const bf16* q_norm_w, const bf16* k_norm_w, float eps);
 void launch_kv_append(const bf16* k, long k_stride, const bf16* v, long v_stride,
                       const int* slots, void* k_cache, void* v_cache, int T, int Hkv, int D,
                       int block_size, hipStream_t stream, int kv_fp8 = 0);

@@ -10,6 +10,11 @@
 //                                          8 consecutive keys of one d as one load)
 // Cache elements are bf16 or FP8 e4m3 (bfly_kv.h); the rotated bf16 values are what is
 // cached, so an FP8 cache holds exactly torch's bf16 -> float8_e4m3fn conversion of them.
+//
+// QKNORM (Qwen3): every Q and K head is RMS-normalised over its D elements and scaled by a [D]
+// weight (q_norm_w for the Q heads, k_norm_w for the K heads, shared by all heads) in front of
+// the rotation: x * rsqrt(mean(x^2) + eps) * w, f32 from the bf16 input to the one rounding of
+// the rotated value.
 #include "bfly_common.h"
 #include "bfly_kernels.h"
 #include "bfly_kv.h"
@@ -27,13 +32,24 @@ constexpr int kRopeThreads = 256;
 // dependent add chain over the 16 slabs of the tp8 B = 1 QKV plan waited a load latency per slab
 // (14 us per launch, profiles/r6_latency.md). The adds keep the slab order (the reduce kernel's
 // sum, bit for bit).
-template <int NC>
+// AS_REDUCE (the QKNORM kernels): the bits of splitk_reduce itself, whatever sk. That kernel is
+// built with -ffast-math like this file, and its loop over the slabs comes out of the compiler
+// two slabs wide: the even and the odd slabs of the first sk & ~1 each in their own chain from 0,
+// the two chains added, then the last slab of an odd sk. The same association here, with
+// reassociation off so that it stays that way. (Without AS_REDUCE the compiler is free to turn a
+// batch's chain into a tree, which is that sum to within an f32 rounding.)
+template <int NC, bool AS_REDUCE>
 __device__ __forceinline__ void slab_sum(const float* __restrict__ prow, int sk, long slab, const int (&col)[NC],
                                          f32x4 (&lo)[NC], f32x4 (&hi)[NC]) {
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
     lo[c] = *reinterpret_cast<const f32x4*>(prow + col[c]);
     hi[c] = *reinterpret_cast<const f32x4*>(prow + col[c] + 4);
+  }
+  [[maybe_unused]] f32x4 lo1[NC], hi1[NC];   // AS_REDUCE: the chain of the odd slabs (lo / hi: the even ones)
+  if constexpr (AS_REDUCE) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) lo1[c] = hi1[c] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   for (int k0 = 1; k0 < sk; k0 += 8) {
     f32x4 l[8][NC], h[8][NC];
@@ -46,15 +62,45 @@ __device__ __forceinline__ void slab_sum(const float* __restrict__ prow, int sk,
         h[j][c] = *reinterpret_cast<const f32x4*>(prow + off + col[c] + 4);
       }
     }
+    if constexpr (AS_REDUCE) {
+#pragma clang fp reassociate(off)
 #pragma unroll
-    for (int j = 0; j < 8; ++j)
-      if (k0 + j < sk) {
+      for (int j = 0; j < 8; ++j) {
+        const int s = k0 + j;          // k0 is odd: slab s is odd for even j
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
-          lo[c] += l[j][c];
-          hi[c] += h[j][c];
+          if (j % 2 == 0) {
+            if (s < sk) { lo1[c] += l[j][c]; hi1[c] += h[j][c]; }
+          } else if (s < (sk & ~1)) {
+            lo[c] += l[j][c];
+            hi[c] += h[j][c];
+          } else if (s < sk) {         // the last slab of an odd sk: every other one is in its chain by now
+            lo[c] = (lo[c] + lo1[c]) + l[j][c];
+            hi[c] = (hi[c] + hi1[c]) + h[j][c];
+          }
         }
       }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (k0 + j < sk) {
+#pragma unroll
+          for (int c = 0; c < NC; ++c) {
+            lo[c] += l[j][c];
+            hi[c] += h[j][c];
+          }
+        }
+    }
+  }
+  if constexpr (AS_REDUCE) {
+#pragma clang fp reassociate(off)
+    if (sk % 2 == 0) {
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        lo[c] += lo1[c];
+        hi[c] += hi1[c];
+      }
+    }
   }
 }
 
@@ -65,15 +111,26 @@ __device__ __forceinline__ bf16x8 pack8(f32x4 lo, f32x4 hi) {
   return a;
 }
 
+// One xor-butterfly step of a sum over the lanes of a head (8 adjacent lanes for D = 128, 4 for
+// D = 64, aligned): DPP quad permutes for xor 1 and xor 2; after them the four lanes of a quad
+// agree, so the mirror of each half row (lane i reads lane 7 - i) stands in for xor 4. Every
+// lane read belongs to the reader's own head, and both partners add the same two values: all
+// lanes of a head end with the same bits.
+template <int CTRL>
+__device__ __forceinline__ float head_dpp_add(float v) {
+  return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
+}
+
 // SLABS: the row comes from the QKV GEMM's split-K slabs (a separate instantiation, so the
 // register-hungry batched slab loads do not cost the plain path occupancy at prefill sizes)
-template <int D, typename CT, bool SLABS>
+template <int D, typename CT, bool SLABS, bool QKNORM>
 __global__ void __launch_bounds__(kRopeThreads)
 rope_kv_kernel(bf16* __restrict__ qkv, const int* __restrict__ positions,
                const float* __restrict__ cos_t, const float* __restrict__ sin_t,
                const int* __restrict__ slots, CT* __restrict__ k_cache,
                CT* __restrict__ v_cache, int Hq, int Hkv, int BS,
-               const float* __restrict__ part, int sk, long slab) {
+               const float* __restrict__ part, int sk, long slab,
+               const bf16* __restrict__ q_norm_w, const bf16* __restrict__ k_norm_w, float eps) {
   constexpr int H2 = D / 2;        // rotation pairs per head
   constexpr int LPH = H2 / 8;      // lanes per head (each lane: 8 pairs)
   constexpr int LPV = D / 8;
@@ -96,7 +153,7 @@ rope_kv_kernel(bf16* __restrict__ qkv, const int* __restrict__ positions,
     if constexpr (SLABS) {
       const int cols[2] = {h * D + p0, h * D + p0 + H2};
       f32x4 lo[2], hi[2];
-      slab_sum<2>(prow, sk, slab, cols, lo, hi);
+      slab_sum<2, QKNORM>(prow, sk, slab, cols, lo, hi);
       a = pack8(lo[0], hi[0]);
       b = pack8(lo[1], hi[1]);
     } else {
@@ -107,13 +164,36 @@ rope_kv_kernel(bf16* __restrict__ qkv, const int* __restrict__ positions,
     const f32x4 c1 = *reinterpret_cast<const f32x4*>(cr + p0 + 4);
     const f32x4 s0 = *reinterpret_cast<const f32x4*>(sr + p0);
     const f32x4 s1 = *reinterpret_cast<const f32x4*>(sr + p0 + 4);
+    // QKNORM: x * (1/rms of the head) * w in f32, from the bf16 values the plain path rotates
+    float inv = 1.f;
+    bf16x8 wa, wb;
+    if constexpr (QKNORM) {
+      const bf16* w = h < Hq ? q_norm_w : k_norm_w;
+      wa = *reinterpret_cast<const bf16x8*>(w + p0);
+      wb = *reinterpret_cast<const bf16x8*>(w + p0 + H2);
+      float ss = 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        ss = __builtin_fmaf(bf2f(a[j]), bf2f(a[j]), ss);
+        ss = __builtin_fmaf(bf2f(b[j]), bf2f(b[j]), ss);
+      }
+      ss = head_dpp_add<0xB1>(ss);                        // quad_perm [1, 0, 3, 2]: lane ^ 1
+      ss = head_dpp_add<0x4E>(ss);                        // quad_perm [2, 3, 0, 1]: lane ^ 2
+      if constexpr (LPH == 8) ss = head_dpp_add<0x141>(ss);   // row_half_mirror: the other quad
+      inv = rsqrtf(ss * (1.f / D) + eps);
+    }
     bf16x8 oa, ob;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float c = j < 4 ? c0[j] : c1[j - 4];
       const float s = j < 4 ? s0[j] : s1[j - 4];
+      float x0 = bf2f(a[j]), x1 = bf2f(b[j]);
+      if constexpr (QKNORM) {
+        x0 = x0 * inv * bf2f(wa[j]);
+        x1 = x1 * inv * bf2f(wb[j]);
+      }
       float r0, r1;
-      rope_rotate(bf2f(a[j]), bf2f(b[j]), c, s, r0, r1);
+      rope_rotate(x0, x1, c, s, r0, r1);
       oa[j] = f2bf(r0);
       ob[j] = f2bf(r1);
     }
@@ -136,7 +216,7 @@ rope_kv_kernel(bf16* __restrict__ qkv, const int* __restrict__ positions,
   if constexpr (SLABS) {
     const int cols[1] = {col};
     f32x4 lo[1], hi[1];
-    slab_sum<1>(prow, sk, slab, cols, lo, hi);
+    slab_sum<1, QKNORM>(prow, sk, slab, cols, lo, hi);
     v = pack8(lo[0], hi[0]);
   } else {
     v = *reinterpret_cast<const bf16x8*>(row + col);
@@ -171,18 +251,19 @@ kv_append_kernel(const bf16* __restrict__ k, long k_stride, const bf16* __restri
   }
 }
 
-template <typename CT>
+template <typename CT, bool QKNORM>
 static void run_rope_kv(bf16* qkv, int T, int Hq, int Hkv, int D, const int* positions,
                         const float* cos_t, const float* sin_t, const int* slots, void* k_cache,
-                        void* v_cache, int block_size, hipStream_t stream, const float* part, int sk) {
+                        void* v_cache, int block_size, hipStream_t stream, const float* part, int sk,
+                        const bf16* q_norm_w, const bf16* k_norm_w, float eps) {
   const long slab = (long)T * (Hq + 2 * Hkv) * D;
   const int items = (Hq + Hkv) * (D / 16) + Hkv * (D / 8);
   const dim3 grid(T, (items + kRopeThreads - 1) / kRopeThreads);
   CT* kc = static_cast<CT*>(k_cache);
   CT* vc = static_cast<CT*>(v_cache);
 #define ROPE_LAUNCH(D_, S_)                                                                             \
-  rope_kv_kernel<D_, CT, S_><<<grid, kRopeThreads, 0, stream>>>(qkv, positions, cos_t, sin_t, slots, kc, vc, \
-                                                                Hq, Hkv, block_size, part, sk, slab)
+  rope_kv_kernel<D_, CT, S_, QKNORM><<<grid, kRopeThreads, 0, stream>>>(                               \
+      qkv, positions, cos_t, sin_t, slots, kc, vc, Hq, Hkv, block_size, part, sk, slab, q_norm_w, k_norm_w, eps)
   if (D == 128) {
     if (part) ROPE_LAUNCH(128, true);
     else ROPE_LAUNCH(128, false);
@@ -199,11 +280,11 @@ void launch_rope_kv(bf16* qkv, int T, int Hq, int Hkv, int D, const int* positio
                     int kv_fp8) {
   if (T <= 0) return;
   if (kv_fp8)
-    run_rope_kv<fp8_t>(qkv, T, Hq, Hkv, D, positions, cos_t, sin_t, slots, k_cache, v_cache, block_size,
-                       stream, part, sk);
+    run_rope_kv<fp8_t, false>(qkv, T, Hq, Hkv, D, positions, cos_t, sin_t, slots, k_cache, v_cache, block_size,
+                              stream, part, sk, nullptr, nullptr, 0.f);
   else
-    run_rope_kv<bf16>(qkv, T, Hq, Hkv, D, positions, cos_t, sin_t, slots, k_cache, v_cache, block_size,
-                      stream, part, sk);
+    run_rope_kv<bf16, false>(qkv, T, Hq, Hkv, D, positions, cos_t, sin_t, slots, k_cache, v_cache, block_size,
+                             stream, part, sk, nullptr, nullptr, 0.f);
 }
 
 template <typename CT>
@@ -229,6 +310,20 @@ void launch_kv_append(const bf16* k, long k_stride, const bf16* v, long v_stride
     run_kv_append<fp8_t>(k, k_stride, v, v_stride, slots, k_cache, v_cache, T, Hkv, D, block_size, stream);
   else
     run_kv_append<bf16>(k, k_stride, v, v_stride, slots, k_cache, v_cache, T, Hkv, D, block_size, stream);
+}
+
+// after the other launchers: the existing kernels keep their places in the code object
+void launch_rope_qknorm_kv(bf16* qkv, int T, int Hq, int Hkv, int D, const int* positions,
+                           const float* cos_t, const float* sin_t, const int* slots, void* k_cache,
+                           void* v_cache, int block_size, hipStream_t stream, const float* part, int sk,
+                           int kv_fp8, const bf16* q_norm_w, const bf16* k_norm_w, float eps) {
+  if (T <= 0) return;
+  if (kv_fp8)
+    run_rope_kv<fp8_t, true>(qkv, T, Hq, Hkv, D, positions, cos_t, sin_t, slots, k_cache, v_cache, block_size,
+                             stream, part, sk, q_norm_w, k_norm_w, eps);
+  else
+    run_rope_kv<bf16, true>(qkv, T, Hq, Hkv, D, positions, cos_t, sin_t, slots, k_cache, v_cache, block_size,
+                            stream, part, sk, q_norm_w, k_norm_w, eps);
 }
 
 }  // namespace bfly
