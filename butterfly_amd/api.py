@@ -67,7 +67,12 @@ def token_logprobs(req) -> tuple:
 class LLM:
     def __init__(self, model: Union[str, ModelConfig], plan: Union[str, dict, PartitionPlan, None] = "auto",
                  engine_config: Optional[EngineConfig] = None, tokenizer: Optional[str] = None,
-                 seed: int = 0, objective: str = "throughput"):
+                 seed: int = 0, objective: str = "throughput", engine_cfg: Optional[EngineConfig] = None):
+        """`engine_cfg`: the same as `engine_config` (the name LLMEngine uses); e.g.
+        EngineConfig(spec_tokens=4) turns on speculative decoding."""
+        if engine_config is not None and engine_cfg is not None:
+            raise ValueError("pass engine_config or engine_cfg, not both")
+        engine_config = engine_config if engine_config is not None else engine_cfg
         rank, world, local = init_distributed()
         if torch.cuda.is_available():
             torch.cuda.set_device(local)

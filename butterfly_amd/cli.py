@@ -48,6 +48,21 @@ def _lora_config(loras: dict, max_rank: int) -> dict:
     return dict(max_loras=len(loras) or None, max_lora_rank=max_rank)
 
 
+def _spec_args(p) -> None:
+    p.add_argument("--spec-tokens", type=int, default=0, metavar="K",
+                   help="speculative decoding: up to K prompt-lookup draft tokens per sequence and step, verified "
+                        "in one step; outputs are those of K = 0 (the default: off)")
+    p.add_argument("--spec-ngram-max", type=int, default=4, help="longest suffix the draft lookup matches")
+    p.add_argument("--spec-ngram-min", type=int, default=2, help="shortest suffix the draft lookup matches")
+    p.add_argument("--spec-max-rows", type=int, default=64,
+                   help="a verify step has at most this many rows (sequences x (1 + longest draft))")
+
+
+def _spec_config(a) -> dict:
+    return dict(spec_tokens=a.spec_tokens, spec_ngram_max=a.spec_ngram_max, spec_ngram_min=a.spec_ngram_min,
+                spec_max_rows=a.spec_max_rows)
+
+
 def cmd_partition(a) -> int:
     from .partition import partition
 
@@ -96,7 +111,8 @@ def cmd_generate(a) -> int:
     llm = LLM(a.model, plan=_strategy(a.plan),
               engine_config=EngineConfig(max_batch=8, max_seq_len=a.max_seq_len, use_graphs=not a.no_graphs,
                                          snapshot_dir=a.snapshot_dir, snapshot_every=snap_every,
-                                         weight_dtype=a.weight_dtype, **_lora_config(loras, a.max_lora_rank)),
+                                         weight_dtype=a.weight_dtype, **_lora_config(loras, a.max_lora_rank),
+                                         **_spec_config(a)),
               tokenizer=a.tokenizer)
     for name, path in loras.items():
         llm.load_lora(name, path)
@@ -147,7 +163,7 @@ def cmd_serve(a) -> int:
     llm = LLM(a.model, plan=_strategy(a.plan), tokenizer=a.tokenizer,
               engine_config=EngineConfig(max_batch=a.max_batch, max_seq_len=a.max_seq_len,
                                          weight_dtype=a.weight_dtype,
-                                         **_lora_config(loras, a.max_lora_rank)))
+                                         **_lora_config(loras, a.max_lora_rank), **_spec_config(a)))
     for name, path in loras.items():
         llm.load_lora(name, path)
     serve(llm, a.host, a.port)
@@ -207,6 +223,11 @@ def cmd_info(a) -> int:
             "kernels_loaded": ops.load_library(), "kernel_lib": ops.library_path(), "weight_dtypes": list(WEIGHT_DTYPES),
             "lora": {"slots": flags.get("BFLY_MAX_LORAS"), "max_rank": EngineConfig().max_lora_rank,
                      "slot_ranks": list(ops.LORA_RANKS)},
+            "spec": {"spec_tokens": EngineConfig().spec_tokens, "spec_ngram_max": EngineConfig().spec_ngram_max,
+                     "spec_ngram_min": EngineConfig().spec_ngram_min, "spec_max_rows": EngineConfig().spec_max_rows,
+                     "proposer": "prompt lookup (n-gram)", "verify_max_columns": 64,
+                     "metrics": ["spec_verify_steps", "spec_verify_sequences", "spec_draft_tokens",
+                                 "spec_accepted_tokens"]},
             "flags": flags.dump()}
     if torch.cuda.is_available():
         p = torch.cuda.get_device_properties(0)
@@ -256,6 +277,7 @@ def main(argv=None) -> int:
                    help="load a LoRA adapter directory (butterfly-lora v1 or PEFT) under NAME; repeatable")
     g.add_argument("--use-lora", default=None, metavar="NAME", help="run the prompts with this adapter")
     g.add_argument("--max-lora-rank", type=int, default=16, help="largest adapter rank the slots hold (up to 64)")
+    _spec_args(g)
     g.add_argument("--snapshot-dir", default=None,
                    help="write request-state snapshots here; a restarted job (launch --max-restarts) resumes from them")
     g.add_argument("--snapshot-every", type=int, default=4, help="engine steps between snapshots")
@@ -275,6 +297,7 @@ def main(argv=None) -> int:
     s.add_argument("--lora", action="append", metavar="NAME=DIR",
                    help="serve a LoRA adapter directory under NAME (a request's \"model\" field selects it); repeatable")
     s.add_argument("--max-lora-rank", type=int, default=16, help="largest adapter rank the slots hold (up to 64)")
+    _spec_args(s)
     b = sub.add_parser("bench", add_help=False)
     b.add_argument("rest", nargs=argparse.REMAINDER)
     b.set_defaults(fn=lambda a: subprocess.call([sys.executable, os.path.join(

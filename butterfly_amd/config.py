@@ -272,6 +272,18 @@ class EngineConfig:
     # replica writes <snapshot_dir>/replica-<dp>.json; LLM(..., resume=dir) replays it
     snapshot_dir: Optional[str] = None
     snapshot_every: int = 0
+    # speculative decoding (engine/spec.py): on a pure decode step every sequence may carry up
+    # to `spec_tokens` draft tokens, proposed by prompt lookup (the tokens that followed the
+    # latest earlier occurrence of the sequence's last spec_ngram_max .. spec_ngram_min tokens),
+    # and one eager verify step scores them all. A draft is accepted exactly when it is the token
+    # the engine would have sampled there, so outputs are those of spec_tokens = 0 (the default:
+    # nothing of this runs). A verify step has at most `spec_max_rows` rows (sequences x
+    # (1 + longest draft)), past which the step is the ordinary decode step. pp == tp == ep == 1,
+    # no context-parallel prefill; the engine then steps synchronously (no async_decode overlap).
+    spec_tokens: int = 0
+    spec_ngram_max: int = 4
+    spec_ngram_min: int = 2
+    spec_max_rows: int = 64
 
 
 def load_config_file(path: str | Path) -> dict:

@@ -42,6 +42,12 @@ class ForwardBatch:
     # LoRA step: int32 [T] adapter slot of every row (outside [0, slots): none). None: no row
     # of the step has an adapter and the forward pass is the plain one.
     lora_idx: Optional[torch.Tensor] = None
+    # speculative verify step (is_prefill False): q_rows > 1 rows per sequence, laid out
+    # [B, q_rows]: row 0 the newest token, rows 1 .. q_lens[b] - 1 its draft tokens at the next
+    # positions, the rest padding (slot -1). ctx_lens keeps the decode meaning for row 0; row t
+    # sees ctx_lens[b] + min(t, q_lens[b] - 1) keys (ops.attn_verify).
+    q_rows: int = 0
+    q_lens: Optional[torch.Tensor] = None        # int32 [B]
 
     @property
     def num_tokens(self) -> int:
@@ -60,7 +66,8 @@ class ForwardBatch:
                             mv(self.ctx_lens), self.max_ctx, mv(self.logits_idx), self.ep_tokens,
                             self.ep_alltoall, self.cp, self.num_decode, self.prefix_lens,
                             mv(self.prefix_cu), mv(self.prefix_tables), self.split_seqs, self.split_rows,
-                            mv(self.cu_fresh), self.max_fresh, self.max_paged, mv(self.lora_idx))
+                            mv(self.cu_fresh), self.max_fresh, self.max_paged, mv(self.lora_idx), self.q_rows,
+                            mv(self.q_lens))
 
 
 def make_prefill_batch(prompts: list[list[int]], slots: list[list[int]], device="cpu",

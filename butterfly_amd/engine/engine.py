@@ -42,12 +42,13 @@ from ..partition.schedule import exec_program
 from ..utils import flags, trace
 from ..utils.health import FaultInjector, StepWatchdog
 from ..utils.metrics import Metrics
-from .batch import empty_batch
+from .batch import ForwardBatch, empty_batch
 from .kv_cache import KVCache, device_kv_budget, kv_blocks_for_budget
 from .model_runner import ModelRunner
 from .pipeline import GroupedScheduler, PipePlan
 from . import state
 from .sampler import Sampler, SamplingParams
+from .spec import NgramProposer, accepted_prefix
 
 
 @dataclass
@@ -109,6 +110,9 @@ class LLMEngine:
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
         self.device = torch.device(device)
+        self.spec_k = self._check_spec(cfg, mesh, engine_cfg, self.device)
+        # the default draft proposer (prompt lookup); any object with propose(tokens, k) -> list
+        self.proposer = NgramProposer(engine_cfg.spec_ngram_max, engine_cfg.spec_ngram_min) if self.spec_k else None
         if stage_layers is None:
             stage_layers = balanced_stages(cfg.num_layers, mesh.pp)
         if mesh.ep > 1 and mesh.pp > 1 and not flags.get("BFLY_PP_ASYNC"):
@@ -200,7 +204,9 @@ class LLMEngine:
         # control plane, which never waits for the device)
         # (context-parallel prefill over the DP replicas, pp == 1, runs inside the asynchronous
         # engine too: a tick that runs one is a CP tick, _pp_tick)
-        self.async_pp = flags.get("BFLY_PP_ASYNC") and (mesh.pp > 1 or bool(engine_cfg.async_decode))
+        # (speculative decoding steps synchronously: a verify step needs the token values of the
+        # step before it on the host, to propose from and to accept against)
+        self.async_pp = flags.get("BFLY_PP_ASYNC") and (mesh.pp > 1 or (bool(engine_cfg.async_decode) and not self.spec_k))
         # mixed steps (chunked prefill riding along decode rows, prefix caching): every layout;
         # in the asynchronous pipeline each group's plans are mixed. Expert-parallel replicas
         # agree per step on the padded row count and on whether any of them runs prompt rows
@@ -251,6 +257,9 @@ class LLMEngine:
                                   shapes=self.model.gemm_shapes(), w8_shapes=self.model.w8_shapes(),
                                   vocab=min(d.vocab, max(0, cfg.vocab_size - d.vocab0)),
                                   weight_dtype=self.weight_dtype)
+            if self.spec_k:
+                ops.reserve_verify_workspace(self.device, engine_cfg.max_batch, self.spec_k, engine_cfg.spec_max_rows,
+                                             d.hq, d.hkv, cfg.head_dim, engine_cfg.max_seq_len)
         buckets = [b for b in engine_cfg.graph_batch_sizes if b <= engine_cfg.max_batch] or [engine_cfg.max_batch]
         if self.async_pp and self.scheduler.group_batch not in buckets:
             buckets.append(self.scheduler.group_batch)    # a full group replays one graph
@@ -291,6 +300,9 @@ class LLMEngine:
         self.requests: dict[int, Request] = {}
         self._ids = itertools.count()
         self.metrics = Metrics()
+        if self.spec_k:
+            for name in ("spec_verify_steps", "spec_verify_sequences", "spec_draft_tokens", "spec_accepted_tokens"):
+                self.metrics.inc(name, 0)
         self.pp_first = coord.pp == 0
         self.pp_last = coord.pp == mesh.pp - 1
         self.faults = FaultInjector()
@@ -305,6 +317,33 @@ class LLMEngine:
         self.cp_min = engine_cfg.cp_prefill_min_tokens if (
             mesh.dp > 1 and mesh.pp == 1 and mesh.ep == 1) else 0
         self._cp_queue: deque = deque()
+
+    @staticmethod
+    def _check_spec(cfg: ModelConfig, mesh: Mesh, e: EngineConfig, device) -> int:
+        """Validate the speculative-decoding settings; returns k = spec_tokens (0: off)."""
+        for name in ("spec_tokens", "spec_ngram_max", "spec_ngram_min", "spec_max_rows"):
+            v = getattr(e, name)
+            if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+                raise ValueError(f"{name} must be a non-negative integer, got {v!r}")
+        if e.spec_ngram_min < 1 or e.spec_ngram_min > e.spec_ngram_max:
+            raise ValueError(f"need 1 <= spec_ngram_min <= spec_ngram_max, got {e.spec_ngram_min}, {e.spec_ngram_max}")
+        k = e.spec_tokens
+        if not k:
+            return 0
+        if mesh.tp > 1 or mesh.pp > 1 or mesh.ep > 1:
+            raise ValueError(f"speculative decoding (spec_tokens > 0) needs tp = pp = ep = 1, got tp={mesh.tp} "
+                             f"pp={mesh.pp} ep={mesh.ep}")
+        if e.cp_prefill_min_tokens > 0:
+            raise ValueError("speculative decoding is not supported with context-parallel prefill "
+                             "(cp_prefill_min_tokens > 0)")
+        g = cfg.num_heads // max(1, cfg.num_kv_heads)
+        if (k + 1) * g > 64:
+            raise ValueError(f"speculative decoding: (spec_tokens + 1) * (heads / kv heads) must be <= 64, got "
+                             f"({k} + 1) * {g}")
+        if torch.device(device).type == "cuda" and cfg.head_dim != 128:
+            raise ValueError(f"speculative decoding on the GPU needs head_dim 128 (the verify attention kernel), "
+                             f"got {cfg.head_dim}")
+        return k
 
     @property
     def lockstep_dp(self) -> bool:
@@ -677,6 +716,10 @@ class LLMEngine:
             out.prefill_tokens = fb.num_tokens
             return out
         else:
+            if self.spec_k:
+                out = self._spec_step(plan, rids, t0)      # None: no draft, an ordinary decode step
+                if out is not None:
+                    return out
             last = [self.requests[r].tokens[-1] for r in rids]
             inp = self.runner.decode_inputs(plan, last)
             if self.mesh.pp > 1:
@@ -742,28 +785,173 @@ class LLMEngine:
             raise RuntimeError(f"rank {self.rank}: non-finite logits at engine step {self.steps_done}")
         lps = self._lp_entries(rids, lp)      # to the host with the ids
         for i, (r, t) in enumerate(zip(rids, new)):
-            req = self.requests[r]
-            req.output.append(int(t))
-            if lps is not None and lps[i] is not None:
-                req.logprobs.append(lps[i])
-            req.n_gen = len(req.output)
-            if req.first_token_time is None:
-                req.first_token_time = now
-            self.scheduler.on_token(r)
-            reason = None
-            if len(req.output) >= req.params.max_tokens:
-                reason = "length"
-            elif not req.params.ignore_eos and (int(t) in req.params.stop_token_ids or
-                                                (self.eos is not None and int(t) == self.eos)):
-                reason = "stop"
-            if reason:
-                req.finished, req.finish_reason, req.finish_time = True, reason, now
-                self.scheduler.finish(r)
-                self._pen_release(r)
+            if self._emit_token(self.requests[r], t, None if lps is None else lps[i], now):
                 finished.append(r)
         dt = time.perf_counter() - t0
         self.metrics.observe_step(kind, len(rids), dt)
         return StepOutput(kind, rids, new, finished, dt, logprobs=lps)
+
+    def _emit_token(self, req: Request, t, lp, now: float) -> bool:
+        """Append one sampled token to its request and apply the finish rules (length, then stop
+        token / EOS); a finished request leaves the scheduler. Returns whether it finished."""
+        r = req.rid
+        req.output.append(int(t))
+        if lp is not None:
+            req.logprobs.append(lp)
+        req.n_gen = len(req.output)
+        if req.first_token_time is None:
+            req.first_token_time = now
+        self.scheduler.on_token(r)
+        reason = None
+        if len(req.output) >= req.params.max_tokens:
+            reason = "length"
+        elif not req.params.ignore_eos and (int(t) in req.params.stop_token_ids or
+                                            (self.eos is not None and int(t) == self.eos)):
+            reason = "stop"
+        if reason:
+            req.finished, req.finish_reason, req.finish_time = True, reason, now
+            self.scheduler.finish(r)
+            self._pen_release(r)
+        return reason is not None
+
+    # ------------------------------------------------------------------------------------
+    # speculative decoding (engine/spec.py)
+    def _spec_drafts(self, plan, rids: list) -> Optional[list]:
+        """Draft tokens per sequence of a pure decode plan, or None when the step should be the
+        ordinary decode step (no sequence has a draft, or the verify step would exceed
+        spec_max_rows). A draft is clamped to the request's remaining tokens and the sequence
+        length, dropped for penalised requests (their history kernel takes one token per step)
+        and cut to the cache pages that are free beyond one page kept back per sequence of the
+        step, so a draft never takes a page the next appends need and never causes a preemption."""
+        e, m, k = self.ecfg, self.kv.manager, self.spec_k
+        B = len(rids)
+        if 2 * B > e.spec_max_rows:
+            return None
+        bs = self.kv.block_size
+        budget = m.num_free - B
+        drafts = []
+        for r in rids:
+            q = self.requests[r]
+            toks = q.tokens
+            d = min(k, q.params.max_tokens - q.n_gen - 1, e.max_seq_len - len(toks) - 1)
+            dr = []
+            if d > 0 and not q.params.needs_penalty:
+                for t in list(self.proposer.propose(toks, d))[:d]:
+                    if not 0 <= int(t) < self.cfg.vocab_size:
+                        break
+                    dr.append(int(t))
+            if dr:
+                n = m.length(r)
+                room = m.blocks_needed(n) * bs - n             # free slots of the last page
+                dr = dr[:max(0, room + max(0, budget) * bs)]
+                budget -= max(0, m.extend_blocks(r, len(dr)))
+            drafts.append(dr)
+        dmax = max(len(d) for d in drafts)
+        if dmax == 0 or B * (1 + dmax) > e.spec_max_rows:
+            return None
+        return drafts
+
+    def _spec_step(self, plan, rids: list, t0: float) -> Optional[StepOutput]:
+        """One eager verify step for a pure decode plan: QN = 1 + longest draft rows per
+        sequence (row 0 the newest token, then its draft tokens at the next positions and fresh
+        cache slots, then padding rows that repeat the last valid row without a slot), logits
+        for all rows, every row sampled as the token of its output index. Per sequence the
+        longest draft prefix equal to the sampled tokens is accepted and a + 1 tokens are
+        emitted through the usual finish rules; the cache slots of the rejected drafts go back
+        (KVBlockManager.truncate). Returns None when the step should be an ordinary decode."""
+        drafts = self._spec_drafts(plan, rids)
+        if drafts is None:
+            return None
+        m = self.kv.manager
+        B, QN = len(rids), 1 + max(len(d) for d in drafts)
+        reqs = [self.requests[r] for r in rids]
+        ids = np.zeros((B, QN), dtype=np.int32)
+        pos = np.zeros((B, QN), dtype=np.int32)
+        slots = np.full((B, QN), -1, dtype=np.int32)
+        qlen = np.zeros((B,), dtype=np.int32)
+        for i, (r, q, dr) in enumerate(zip(rids, reqs, drafts)):
+            d = len(dr)
+            p0 = int(plan.decode_positions[i])
+            ids[i, 0], pos[i, 0], slots[i, 0] = q.tokens[-1], p0, plan.decode_slots[i]
+            if d:
+                ids[i, 1:1 + d] = dr
+                pos[i, 1:1 + d] = np.arange(p0 + 1, p0 + 1 + d)
+                slots[i, 1:1 + d] = m.extend(r, d)
+            ids[i, 1 + d:], pos[i, 1 + d:] = ids[i, d], pos[i, d]
+            qlen[i] = 1 + d
+        rn = self.runner
+        m.fill_decode_tables(rids, rn._tables_host[:B], rn._ctx_host[:B])     # tables with the draft pages
+        dev = self.device
+        t32 = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev, non_blocking=True)  # noqa: E731
+        lora = rn._lora_rows(rids, [QN] * B)
+        # max_ctx: max_ctx + QN - 1 bounds every sequence's keys, and no sequence has more than
+        # max_seq_len (the block table's width)
+        fb = ForwardBatch(input_ids=t32(ids.reshape(-1)), positions=t32(pos.reshape(-1)), slots=t32(slots.reshape(-1)),
+                          is_prefill=False, block_tables=t32(rn._tables_host[:B].copy()), ctx_lens=t32(pos[:, 0] + 1),
+                          max_ctx=rn.max_seq_len - (QN - 1), logits_idx=None, q_rows=QN, q_lens=t32(qlen),
+                          lora_idx=None if lora is None else t32(lora))
+        logits = self._maybe_poison(rn.run(fb))
+        # every row sampled by the sampler as it is: row t with the seed of output index n_gen + t
+        V = logits.shape[-1]
+        temps = [q.params.temperature for q in reqs for _ in range(QN)]
+        if all(t <= 0 for t in temps):
+            tt = seeds = params = None
+        else:
+            tt = torch.tensor(temps, dtype=torch.float32, device=dev)
+            seeds = torch.tensor([(q.params.seed or r) * 1000003 + q.n_gen + t for r, q in zip(rids, reqs)
+                                  for t in range(QN)], dtype=torch.int64, device=dev)
+            params = [q.params for q in reqs for _ in range(QN)]
+        check = bool(self.nan_check)
+        sampled = self.sampler.sample(logits, tt, seeds, params, check_finite=check)
+        if any(q.params.needs_penalty for q in reqs):
+            # penalised requests carry no draft: their row 0 is sampled from the penalised logits
+            # exactly as a decode step samples it
+            l0 = logits.view(B, QN, V)[:, 0].contiguous()
+            t0s, s0, p0s = self._sample_params(rids)
+            ids0 = self.sampler.sample(self._penalise(l0, rids), t0s, s0, p0s, check_finite=check)
+            pen = torch.tensor([i * QN for i, q in enumerate(reqs) if q.params.needs_penalty], dtype=torch.int64, device=dev)
+            sampled = sampled.clone()
+            sampled[pen] = ids0[pen // QN]
+        ns = [q.params.logprobs for q in reqs if q.params.logprobs is not None]
+        lp = self.sampler.logprobs(logits, sampled, max(ns)) if ns else None
+        if lp is not None:
+            if any(t.is_cuda for t in lp):
+                lp = ops.logprobs_to_host(lp)
+            lp = tuple(t.tolist() for t in lp)
+        sampled = sampled.view(B, QN).tolist()
+        now = time.perf_counter()
+        out_rids, out_new, out_lps, finished = [], [], [], []
+        n_draft = n_acc = 0
+        for i, (r, q, dr) in enumerate(zip(rids, reqs, drafts)):
+            a = accepted_prefix(dr, sampled[i])
+            if any(int(t) < 0 for t in sampled[i][:a + 1]):
+                raise RuntimeError(f"rank {self.rank}: non-finite logits at engine step {self.steps_done}")
+            n_draft += len(dr)
+            n_acc += a
+            base = int(plan.decode_positions[i]) + 1      # the sequence's length after its append
+            done = False
+            for t in range(a + 1):
+                entry = None
+                n = q.params.logprobs
+                if lp is not None and n is not None:
+                    row = i * QN + t
+                    entry = (lp[0][row], [(x, v) for x, v in zip(lp[1][row][:n], lp[2][row][:n]) if x >= 0])
+                out_rids.append(r)
+                out_new.append(int(sampled[i][t]))
+                out_lps.append(entry)
+                done = self._emit_token(q, sampled[i][t], entry, now)
+                if done:
+                    finished.append(r)
+                    break
+            if not done:
+                m.truncate(r, base + a)                   # the rejected drafts' slots go back
+        self.metrics.inc("spec_verify_steps")
+        self.metrics.inc("spec_verify_sequences", B)
+        self.metrics.inc("spec_draft_tokens", n_draft)
+        self.metrics.inc("spec_accepted_tokens", n_acc)
+        dt = time.perf_counter() - t0
+        self.metrics.observe_step("verify", len(out_new), dt)
+        return StepOutput("verify", out_rids, out_new, finished, dt, logprobs=out_lps if lp is not None else None)
 
     def _ep_agree(self, plan) -> tuple:
         """Expert-parallel step agreement (host integers over the control plane, no device

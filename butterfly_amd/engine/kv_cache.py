@@ -49,6 +49,12 @@ class KVCache:
     def bytes(self) -> int:
         return sum(k.numel() * k.element_size() + v.numel() * v.element_size() for k, v in self.layers)
 
+    def truncate(self, sid: int, new_len: int) -> None:
+        """Give back the slots of a sequence past `new_len` (the K/V of rejected draft tokens of a
+        speculative verify step): pages wholly beyond it are released, ref-counted, so shared and
+        prefix-cached pages only lose this sequence's reference."""
+        self.manager.truncate(sid, new_len)
+
     def copy_blocks(self, pairs: list) -> None:
         """Copy-on-write page copies (src -> dst) before a step that writes to a forked page."""
         for src, dst in pairs:

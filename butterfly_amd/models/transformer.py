@@ -707,6 +707,10 @@ class TransformerLM:
                 attn = self._mixed_attention(q, k, v, fb, kc, vc)
             else:
                 attn = ops.attn_prefill(q, k, v, fb.cu_seqlens, fb.max_seqlen, self.scale, True)
+        elif fb.q_rows > 1:
+            # speculative verify step: q_rows rows per sequence over one stream of its pages
+            attn = ops.attn_verify(q.view(T // fb.q_rows, fb.q_rows, d.hq, D), kc, vc, fb.block_tables, fb.ctx_lens,
+                                   fb.q_lens, self.scale, fb.max_ctx)
         else:
             attn = ops.attn_decode(q, kc, vc, fb.block_tables, fb.ctx_lens, self.scale, fb.max_ctx)
         return self._o_proj(pre, attn, T)

@@ -924,6 +924,60 @@ def attn_decode(q, k_cache, v_cache, block_tables, ctx_lens, scale: float, max_c
     return out
 
 
+def attn_verify_partials(B: int, QN: int, Hq: int, Hkv: int, D: int, max_ctx: int, part_tokens: int = 0):
+    """(part_tokens, splits, part_o elements, part_ml elements) of an attn_verify call."""
+    keys = max_ctx + QN - 1
+    if part_tokens <= 0:
+        part_tokens = torch.ops.bfly.attn_decode_part_tokens(B, Hkv, keys)
+    ns = torch.ops.bfly.attn_decode_splits(keys, part_tokens)
+    nc = 16 * torch.ops.bfly.attn_verify_tiles(QN, Hq // Hkv)
+    return part_tokens, ns, B * Hkv * ns * nc * D, B * Hkv * ns * nc * 2
+
+
+def reserve_verify_workspace(device, max_batch: int, spec_tokens: int, max_rows: int, num_heads: int,
+                             num_kv_heads: int, head_dim: int, max_ctx: int) -> None:
+    """Size the split partials of every attn_verify shape an engine's verify steps can take: up
+    to `max_batch` sequences of 2 .. spec_tokens + 1 rows, at most `max_rows` rows in all."""
+    if not load_library():
+        return
+    n_o = n_ml = 0
+    for qn in range(2, spec_tokens + 2):
+        for b in range(1, min(max_batch, max_rows // qn) + 1):
+            _, ns, o, ml = attn_verify_partials(b, qn, num_heads, num_kv_heads, head_dim, max_ctx)
+            if ns > 1:
+                n_o, n_ml = max(n_o, o), max(n_ml, ml)
+    if n_o:
+        _arena.get(device, "attn_o", n_o, torch.float32)
+        _arena.get(device, "attn_ml", n_ml, torch.float32)
+
+
+def attn_verify(q, k_cache, v_cache, block_tables, ctx_lens, q_lens, scale: float, max_ctx: int,
+                part_tokens: int = DECODE_PART_TOKENS, out=None):
+    """Multi-query paged decode attention of a speculative verify step (attention_verify.hip).
+    q [B, QN, Hq, D]: row 0 of a sequence is its newest token, rows 1 .. q_lens[b] - 1 its draft
+    tokens, whose K/V rope_kv has already appended. Row t sees keys
+    [0, ctx_lens[b] + min(t, q_lens[b] - 1)) (ctx_lens as in attn_decode: what row 0 sees);
+    rows t >= q_lens[b] are padding, computed with the last valid row's limit. `max_ctx` is the
+    static bound (it fixes the split grid): max_ctx + QN - 1 bounds every sequence's largest
+    limit ctx_lens[b] + q_lens[b] - 1, so max_ctx bounds ctx_lens where q_lens[b] = QN.
+    QN * (Hq / Hkv) <= 64. The K/V pages are streamed once for all rows."""
+    if not _gpu(q):
+        return ref.attn_verify(q, k_cache, v_cache, block_tables, ctx_lens, q_lens, scale, max_ctx,
+                               part_tokens, out)
+    B, QN, Hq, D = q.shape
+    Hkv = k_cache.shape[1]
+    if out is None:
+        out = _empty(B, QN, Hq, D, dtype=q.dtype, device=q.device)
+    part_tokens, ns, n_o, n_ml = attn_verify_partials(B, QN, Hq, Hkv, D, int(max_ctx), int(part_tokens))
+    po = pml = None
+    if ns > 1:
+        po = _arena.get(q.device, "attn_o", n_o, torch.float32)
+        pml = _arena.get(q.device, "attn_ml", n_ml, torch.float32)
+    torch.ops.bfly.attn_verify(q, k_cache, v_cache, block_tables, ctx_lens, q_lens, float(scale), int(max_ctx),
+                               part_tokens, out, po, pml)
+    return out
+
+
 def init_hash_(out, grow0: int, gcol0: int, gcols: int, seed: int, amp: float):
     """Fill a 2-D (view of a) weight shard with partition-independent hashed uniform values."""
     if not _gpu(out):

@@ -630,6 +630,25 @@ def attn_decode(q, k_cache, v_cache, block_tables, ctx_lens, scale, max_ctx=None
     return out
 
 
+def attn_verify(q, k_cache, v_cache, block_tables, ctx_lens, q_lens, scale, max_ctx=None,
+                part_tokens=None, out=None, **_):
+    """q [B, QN, Hq, D] (speculative verify step: row 0 the newest token, rows 1.. the drafts)
+    against the paged cache, which already holds every row's K/V. Row t of sequence b sees keys
+    [0, ctx_lens[b] + min(t, q_lens[b] - 1)); rows t >= q_lens[b] are padding and repeat the
+    last valid row's limit. Each row is attn_decode's arithmetic at that row's limit."""
+    B, QN, Hq, D = q.shape
+    res = torch.empty(B, QN, Hq, D, dtype=q.dtype, device=q.device)
+    cl = ctx_lens.long()
+    ql = q_lens.long().clamp(1, QN)
+    for t in range(QN):
+        lim = cl[:B] + torch.clamp(ql[:B] - 1, max=t)
+        res[:, t] = attn_decode(q[:, t], k_cache, v_cache, block_tables, lim, scale)
+    if out is None:
+        return res
+    out.copy_(res.view(out.shape))
+    return out
+
+
 def attn_prefill_paged(q, k_cache, v_cache, tables, cu_q, positions, max_q, scale, out=None):
     """Chunked prefill over the paged cache: rows [cu_q[s], cu_q[s+1]) of sequence s (query
     positions `positions[row]`) attend causally to keys [0, positions[row]] of the sequence,

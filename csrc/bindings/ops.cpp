@@ -964,6 +964,52 @@ void attn_decode(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, 
   TORCH_CHECK(rc == 0, "attn_decode: unsupported configuration (rc=", rc, ")");
 }
 
+// Multi-query paged decode attention of a speculative verify step (attention_verify.hip):
+// q [B, QN, Hq, D] (rows may be strided, as a view into fused QKV rows), out [B, QN, Hq, D]
+// dense. Row t of sequence b sees keys [0, ctx_lens[b] + min(t, q_lens[b] - 1)); max_ctx bounds
+// ctx_lens. Splits: attn_decode_part_tokens / attn_decode_splits over max_ctx + QN - 1 keys.
+int64_t attn_verify_tiles(int64_t QN, int64_t G) { return bfly::attn_verify_tiles((int)QN, (int)G); }
+
+void attn_verify(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& block_tables,
+                 const Tensor& ctx_lens, const Tensor& q_lens, double scale, int64_t max_ctx, int64_t part_tokens,
+                 Tensor& out, const OptTensor& part_o, const OptTensor& part_ml) {
+  const Op op("attn_verify", q, "q");
+  op.check(q, "q", {at::kBFloat16});
+  op.check_shape(q, "q", {-1, -1, -1, -1});
+  const int64_t B = q.size(0), QN = q.size(1), Hq = q.size(2), D = q.size(3);
+  TORCH_CHECK(QN >= 1 && B < (1LL << 20) && B * QN < (1LL << 24), "attn_verify: q [B, QN >= 1, Hq, D]");
+  TORCH_CHECK(QN == 1 || B <= 1 || q.stride(0) == QN * q.stride(1), "attn_verify: q rows b * QN + t must be evenly strided, got strides ",
+              q.strides());
+  const Rows<bf16> qr = op.heads<bf16>(at::as_strided(q, {B * QN, Hq, D}, {QN == 1 ? q.stride(0) : q.stride(1), q.stride(2), q.stride(3)}),
+                                       "q", {B * QN, Hq, D}, kAlign16 | kLd8);
+  const KvCaches kv = kv_caches(op, k_cache, v_cache, -1, D);
+  TORCH_CHECK(D == 128 && kv.BS == 32, "attn_verify: head_dim 128 and 32-token pages, got D=", D, " BS=", kv.BS);
+  TORCH_CHECK(kv.Hkv > 0 && Hq % kv.Hkv == 0 && QN * (Hq / kv.Hkv) <= 64, "attn_verify: QN * (Hq / Hkv) must be <= 64, got QN=", QN,
+              " Hq=", Hq, " Hkv=", kv.Hkv);
+  TORCH_CHECK(max_ctx >= 0 && max_ctx < (1LL << 30), "attn_verify: max_ctx");
+  const int keys = (int)(max_ctx + QN - 1);
+  const Rows<int> bt = op.rows<int>(block_tables, "block_tables", {-1, -1});
+  TORCH_CHECK(block_tables.size(0) >= B, "attn_verify: block_tables has fewer rows than q");
+  TORCH_CHECK((long)block_tables.size(1) * kv.BS >= keys, "attn_verify: block table too narrow for max_ctx + QN - 1");
+  if (part_tokens <= 0) part_tokens = bfly::attn_decode_part_tokens(B, kv.Hkv, keys);
+  TORCH_CHECK(part_tokens % kv.BS == 0, "attn_verify: part_tokens must be a multiple of the page size");
+  const int nsplit = bfly::attn_decode_splits(keys, part_tokens);
+  const int NC = 16 * bfly::attn_verify_tiles(QN, Hq / kv.Hkv);
+  float *po = nullptr, *pml = nullptr;
+  if (nsplit > 1) {
+    TORCH_CHECK(part_o.has_value() && part_ml.has_value(), "attn_verify: partial buffers required");
+    po = op.flat_min<float>(*part_o, "part_o", (long)B * kv.Hkv * nsplit * NC * D);
+    pml = op.flat_min<float>(*part_ml, "part_ml", (long)B * kv.Hkv * nsplit * NC * 2);
+  }
+  const int* cl = op.flat_min<int>(ctx_lens, "ctx_lens", B);
+  const int* qlp = op.flat_min<int>(q_lens, "q_lens", B);
+  bf16* o = op.shaped<bf16>(out, "out", {B, QN, Hq, D});
+  auto g = op.guard();
+  const int rc = bfly::launch_attn_verify(qr.p, qr.ld, kv.k, kv.v, bt.p, bt.ld, cl, qlp, B, QN, Hq, kv.Hkv, D, kv.BS,
+                                          (float)scale, max_ctx, part_tokens, o, po, pml, cur_stream(), kv.fp8);
+  TORCH_CHECK(rc == 0, "attn_verify: unsupported configuration (rc=", rc, ")");
+}
+
 // Chunked prefill over the paged cache (attention_paged.hip): q [T, Hq, D] rows grouped per
 // sequence by cu_q, positions [T] their absolute positions, tables [nseq, max_blocks].
 void attn_prefill_paged(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& tables,
@@ -1384,6 +1430,10 @@ TORCH_LIBRARY(bfly, m) {
   m.def("lora_splitk(int T, int K) -> int", [](int64_t T, int64_t K) -> int64_t { return bfly::lora_splitk((int)T, (int)K); });
   m.def("lora_check(int K, int J, int N, int R) -> int",
         [](int64_t K, int64_t J, int64_t N, int64_t R) -> int64_t { return bfly::lora_check((int)K, (int)J, (int)N, (int)R); });
+  m.def("attn_verify(Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, Tensor ctx_lens, Tensor q_lens, "
+        "float scale, int max_ctx, int part_tokens, Tensor(a!) out, Tensor(b!)? part_o, Tensor(c!)? part_ml) -> ()",
+        &attn_verify);
+  m.def("attn_verify_tiles(int QN, int G) -> int", &attn_verify_tiles);
   m.def("gemm_with_plan(Tensor x, Tensor w, Tensor(a!) out, int[] plan, int epilogue, Tensor(b!)? workspace, "
         "Tensor? bias=None, bool packed=False) -> ()");
   m.def("gemm_plan_check(int[] plan, int M, int N, int K, int epilogue, bool packed=False) -> int", &gemm_plan_check);

@@ -270,6 +270,15 @@ int launch_attn_decode(const bf16* q, long q_stride, const void* k_cache, const 
                        int Hkv, int D, int block_size, float scale, int max_ctx, int part_tokens,
                        bf16* out, float* part_o, float* part_ml, hipStream_t stream,
                        int kv_fp8 = 0);            // caches hold FP8 e4m3 (bfly_kv.h)
+// Multi-query paged decode attention of a speculative verify step (attention_verify.hip):
+// q rows b * QN + t, row t of sequence b sees keys [0, ctx_lens[b] + min(t, q_lens[b] - 1)).
+// QT = attn_verify_tiles(QN, Hq / Hkv) in 1 .. 4; the split geometry is attn_decode_part_tokens /
+// attn_decode_splits over max_ctx + QN - 1 keys; partials carry 16 QT columns per split.
+int attn_verify_tiles(int QN, int G);
+int launch_attn_verify(const bf16* q, long q_stride, const void* k_cache, const void* v_cache,
+                       const int* block_tables, int bt_stride, const int* ctx_lens, const int* q_lens, int B,
+                       int QN, int Hq, int Hkv, int D, int block_size, float scale, int max_ctx, int part_tokens,
+                       bf16* out, float* part_o, float* part_ml, hipStream_t stream, int kv_fp8 = 0);
 int launch_attn_prefill(const bf16* q, long q_stride, const bf16* k, long k_stride, const bf16* v,
                         long v_stride, const int* cu_seqlens, int nseq, int max_seqlen, int Hq,
                         int Hkv, int D, float scale, bool causal, bf16* out, long o_stride,

@@ -29,6 +29,7 @@ void register_kv_manager(py::module_& m) {
       .def("append_slot", &KVBlockManager::append_slot)
       .def("extend", &KVBlockManager::extend)
       .def("extend_blocks", &KVBlockManager::extend_blocks)
+      .def("truncate", &KVBlockManager::truncate, py::arg("sid"), py::arg("new_len"))
       .def("can_append", &KVBlockManager::can_append)
       .def("fork", &KVBlockManager::fork)
       .def("free", &KVBlockManager::free)

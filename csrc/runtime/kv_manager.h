@@ -134,6 +134,22 @@ class KVBlockManager {
     return blocks_needed(s.len + tokens) - (int)s.blocks.size();
   }
 
+  // Give back the slots past `new_len` (speculative decoding: the K/V of rejected draft tokens).
+  // Sets the length and releases every page wholly beyond it through the ref-counted path, so
+  // a page another sequence still holds, or one registered in the prefix cache, only loses this
+  // sequence's reference (a registered page is parked in the LRU, as when its owner is freed).
+  // Callers never go below the prompt, so registered full prompt pages stay in the sequence.
+  void truncate(int64_t sid, int64_t new_len) {
+    Seq& s = get(sid);
+    if (new_len < 0 || new_len > s.len) throw std::invalid_argument("truncate: new_len must be in [0, len]");
+    const size_t keep = (size_t)blocks_needed(new_len);
+    while (s.blocks.size() > keep) {
+      release(s.blocks.back());
+      s.blocks.pop_back();
+    }
+    s.len = new_len;
+  }
+
   // Reserve the slot for one more token. Returns (slot, cow_src, cow_dst): when the last page
   // is shared, a fresh page is taken and the caller must copy cow_src -> cow_dst first.
   std::tuple<int32_t, int32_t, int32_t> append_slot(int64_t sid) {
